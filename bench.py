@@ -50,6 +50,13 @@ few ms -- each rank reports CPU cores per thread group, IO-thread us per
 request and its GPU's ``gpu_busy_percent`` (sampled every 10 ms through the
 timed window too); rank 0's JSON carries all ranks' figures under
 ``diagnostics``.
+
+Plain and full runs.  A plain run sets up, pre-warms, warms up, times the K
+steps, writes its outputs when ``--dump-outputs DIR`` is given (see
+``dump_outputs``) and prints the result line.  ``--full`` adds the phases
+that take runs of their own after the timed window: the reference-client
+phase (``ref_client_rps``, ``ref_client_gpu_share``) and the concurrency-1
+latency probe (``p50_c1_ms``).
 """
 from __future__ import annotations
 
@@ -132,11 +139,21 @@ def parse():
     ap.add_argument("--reload-cycles", type=int, default=3, help="--model multi: BERT drop/re-add cycles")
     ap.add_argument("--bert-requests", type=int, default=2000, help="--model multi: BERT calls per phase")
     ap.add_argument("--seq-len", type=int, default=128)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed window also run the phases that take runs of their own: the "
+                         "concurrency-1 latency probe (--c1-requests) and the reference-client phase "
+                         "(--ref-client-requests).  Off by default: a plain run sets up, warms up, times "
+                         "--steps steps and prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the Predict outputs of one step's requests, sent once more "
+                         "through the serving path (the load generator drops response payloads; one array "
+                         "per output alias, rows in request order) as DIR/<alias>.npy in float32 / "
+                         "float64 (rank 0's; at most 64 MB in all, a fixed seeded sample of anything larger)")
     ap.add_argument("--c1-requests", type=int, default=200,
-                    help="after the timed window: batch-1 round trips at concurrency 1 over one connection "
-                         "(reported as p50_c1_ms; 0 = skip)")
+                    help="--full: after the timed window, batch-1 round trips at concurrency 1 over one "
+                         "connection (reported as p50_c1_ms; 0 = skip)")
     ap.add_argument("--ref-client-requests", type=int, default=20000,
-                    help="after the timed window: rank 0 drives this many Predicts over 2 HTTP/2 connections "
+                    help="--full: after the timed window, rank 0 drives this many Predicts over 2 HTTP/2 connections "
                          "(the reference client's channel pattern, src/lib.rs:132-138) with min(concurrency, 128) "
                          "x N calls in flight while every rank serves; reported as ref_client_rps + the share each "
                          "GPU served (per-stream routing; 0 = skip)")
@@ -245,6 +262,11 @@ def main():
     exit_code = 0
     if args.device == "cpu":
         args.c1_requests = min(args.c1_requests, 20)
+    if not args.full:
+        # a plain run does only what the headline figure needs
+        args.c1_requests = args.ref_client_requests = 0
+    if args.dump_outputs and args.model == "multi":
+        sys.exit("bench.py: --dump-outputs is not available with --model multi")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(launch_ranks(args))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -484,6 +506,10 @@ def main():
     if thread_pins is not None:
         cpu_report["thread_pins"] = thread_pins
     gpu_busy = busy.stop()
+    if args.dump_outputs and rank == 0:
+        # the window is closed and measured; the load generator still runs, so
+        # these requests are batched with its traffic exactly as the timed ones were
+        dump_outputs(args.dump_outputs, server.port, [bodies[i % len(bodies)] for i in range(per_step)])
     loadgen.stop(30.0)
     # close the window's 16 connections (their socket buffers, up to 4 MB per
     # direction on each side) before the reference-client phase: after a long
@@ -678,6 +704,58 @@ def main():
         os._exit(exit_code)
     if exit_code:
         sys.exit(exit_code)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir: str, port: int, step_bodies: list) -> dict:
+    """``--dump-outputs``: what a caller of the timed path receives for one step.
+
+    The load generator counts response bytes and drops them, so once the timed
+    window is closed, and while the load generator keeps the pipeline as full
+    as it was inside the window, one step's requests (the same pre-encoded
+    bodies, in the same round-robin order) are sent once more through the
+    same port, front end, batcher and kernels.  They share the server's
+    batches with the generator's traffic, as every timed request did, and the
+    decoded PredictResponse outputs are stacked in request order: one
+    ``<alias>.npy`` per output alias, float32 (float64 for 64-bit types).
+    The bodies come from a seeded generator and the weights from a seeded
+    export, so two builds run with the same arguments answer the same inputs
+    (a batch the batcher cuts short runs other tile picks: such rows can
+    differ in the last bf16 bits from run to run).
+    Arrays that together exceed 64 MB are cut to a fixed, seeded sample of
+    their flattened elements."""
+    import asyncio
+
+    from rust_tensorflow_serving2_amd.client import TensorflowServing
+    from rust_tensorflow_serving2_amd.schema import serving
+    from rust_tensorflow_serving2_amd.utils import tensors as T
+
+    async def go():
+        async with await TensorflowServing.new().hostname("127.0.0.1").port(port).build() as c:
+            return await asyncio.gather(*[c._call("tensorflow.serving.PredictionService", "Predict", b, None, 120.0)
+                                          for b in step_bodies])
+    rows = {}
+    for raw in asyncio.run(go()):
+        for alias, tp in serving.PredictResponse.FromString(raw).outputs.items():
+            rows.setdefault(alias, []).append(np.asarray(T.tensor_proto_to_numpy(tp)))
+    arrays = {}
+    for alias, parts in sorted(rows.items()):
+        a = np.concatenate([p.reshape((1,) + p.shape) if p.ndim == 0 else p for p in parts], axis=0)
+        arrays[alias] = a.astype(np.float64 if a.dtype.itemsize > 4 else np.float32)
+    if not arrays:
+        raise SystemExit("--dump-outputs: the responses held no outputs")
+    if sum(a.nbytes for a in arrays.values()) > DUMP_LIMIT_BYTES:
+        share = DUMP_LIMIT_BYTES // len(arrays)
+        for alias, a in arrays.items():
+            if a.nbytes > share:
+                keep = np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))
+                arrays[alias] = a.reshape(-1)[keep]
+    os.makedirs(out_dir, exist_ok=True)
+    for alias, a in arrays.items():
+        np.save(os.path.join(out_dir, alias.replace("/", "_") + ".npy"), a)
+    return {alias: list(a.shape) for alias, a in arrays.items()}
 
 
 def rccl_problems(reports, world: int) -> list:

@@ -27,7 +27,7 @@ def test_bench_gpus2_self_launch_cpu(tmp_path):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env["TMPDIR"] = str(tmp_path)
     cmd = [sys.executable, BENCH, "--gpus", "2", "--device", "cpu", "--model", "tiny", "--image-size", "32",
-           "--steps", "4", "--warmup", "1", "--prewarm-s", "0.2", "--ref-client-requests", "64",
+           "--full", "--steps", "4", "--warmup", "1", "--prewarm-s", "0.2", "--ref-client-requests", "64",
            "--c1-requests", "10", "--io-threads", "2", "--client-threads", "1", "--connections", "2",
            "--lanes", "2"]
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=280, cwd=str(tmp_path))
@@ -85,7 +85,7 @@ def test_bench_gpus8_self_launch_cpu(tmp_path):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env["TMPDIR"] = str(tmp_path)
     cmd = [sys.executable, BENCH, "--gpus", "8", "--device", "cpu", "--model", "tiny", "--image-size", "32",
-           "--steps", "4", "--warmup", "1", "--prewarm-s", "0.2", "--ref-client-requests", "512",
+           "--full", "--steps", "4", "--warmup", "1", "--prewarm-s", "0.2", "--ref-client-requests", "512",
            "--c1-requests", "10", "--io-threads", "1", "--client-threads", "1", "--connections", "2",
            "--lanes", "2"]
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=880, cwd=str(tmp_path))
@@ -109,6 +109,45 @@ def test_bench_gpus8_self_launch_cpu(tmp_path):
         for phase in (d["timed"], d["ref_client"]):
             r = phase.get("router") or {}
             assert r.get("orphaned", 0) == 0 and r.get("lost", 0) == 0, r
+
+
+@pytest.mark.timeout(300)
+def test_bench_plain_run_is_lean_and_dumps_outputs_cpu(tmp_path):
+    """A plain run times exactly --steps steps and skips the phases that
+    ``--full`` adds; ``--dump-outputs`` writes one step's Predict outputs as
+    float arrays that answer the same inputs from run to run."""
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
+    env["TMPDIR"] = str(tmp_path)
+    outs = []
+    for d in ("a", "b"):
+        cmd = [sys.executable, BENCH, "--gpus", "1", "--device", "cpu", "--model", "tiny", "--image-size", "32",
+               "--steps", "5", "--warmup", "1", "--prewarm-s", "0.2", "--batch", "8", "--io-threads", "2",
+               "--client-threads", "1", "--connections", "2", "--lanes", "2", "--dump-outputs", str(tmp_path / d)]
+        p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=280, cwd=str(tmp_path))
+        assert p.returncode == 0, p.stderr[-3000:]
+        outs.append(_json_line(p.stdout))
+    out = outs[0]
+    assert out["steps"] == 5 and out["errors"] == 0 and out["value"] > 0 and out["ms_per_step"] > 0
+    assert out["diagnostics"][0]["rank_timing"]["ok"] == 5 * 8            # --steps sets the timed steps
+    assert out["p50_c1_ms"] is None and "ref_client_rps" not in out       # only with --full
+    assert {"metric", "unit", "higher_is_better", "dtype"} <= set(out)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b")) and "probabilities.npy" in names
+    total = 0
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype in (np.float32, np.float64) and a.shape[0] == 8 and np.isfinite(a).all()
+        # same inputs, same weights; the dynamic batcher may cut the step into other batch sizes, whose
+        # fp32 sums run in another order (eps 6e-8 over a few thousand terms: far inside 1e-4 relative)
+        assert np.allclose(a, b, rtol=1e-4, atol=1e-7), n
+        total += a.nbytes
+    assert 0 < total <= 64 << 20
+    probs = np.load(tmp_path / "a" / "probabilities.npy")
+    assert probs.shape == (8, 1001) and np.allclose(probs.sum(axis=1), 1.0, atol=1e-4)
+    # four distinct request bodies, used round-robin: rows repeat with period 4 and differ within it
+    assert np.allclose(probs[:4], probs[4:], rtol=1e-4, atol=1e-7)
+    assert not np.allclose(probs[0], probs[1], rtol=1e-2, atol=1e-7)
 
 
 def test_rccl_problems_flags_silent_fallbacks():
