@@ -589,11 +589,17 @@ __global__ __launch_bounds__(256) void attention_flash_kernel(const uint16_t* __
     for (int r = 0; r < 4; ++r)
 #pragma unroll
       for (int off = 1; off < 16; off <<= 1) bm[r] = fmaxf(bm[r], __shfl_xor(bm[r], off, 64));
-    float alpha[4], bs[4];
+    // ms: the max the exponentials subtract.  A row whose keys so far are all
+    // closed with a -inf adder has mn = -inf; (-inf) - (-inf) would be NaN in
+    // alpha and in every p of the block, and the NaN would outlive later open
+    // keys.  Subtracting 0 instead gives alpha = 0 and p = exp(-inf) = 0, and
+    // the first block with an open key rescales from there.
+    float alpha[4], bs[4], ms[4];
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const float mn = fmaxf(m[r], bm[r]);
-      alpha[r] = __expf(m[r] - mn);            // exp(-inf) = 0 on the first block
+      ms[r] = mn == -INFINITY ? 0.f : mn;
+      alpha[r] = __expf(m[r] - ms[r]);         // exp(-inf) = 0 on the first block
       m[r] = mn;
       bs[r] = 0.f;
     }
@@ -601,7 +607,7 @@ __global__ __launch_bounds__(256) void attention_flash_kernel(const uint16_t* __
     for (int nt = 0; nt < FKB / 16; ++nt)
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const float e = __expf(sc[nt][r] - m[r]);
+        const float e = __expf(sc[nt][r] - ms[r]);
         bs[r] += e;
         pw[(fq * 4 + r) * P_LD + nt * 16 + fr] = f32_to_bf16(e);
       }

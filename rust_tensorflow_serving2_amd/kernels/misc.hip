@@ -235,7 +235,10 @@ __global__ __launch_bounds__(256) void softmax_argmax_kernel(const void* __restr
     }
     for (int c = PER * 256 + tid; c < cols; c += 256) probs[long(row) * cols + c] = __expf(load(c) - mx) * inv;
   }
-  if (classes && tid == 0) classes[row] = arg;
+  // a row of NaNs wins no comparison and leaves arg at its sentinel: class 0
+  // then (what an argmax that treats NaN as the maximum returns for such a
+  // row), never an index outside [0, cols)
+  if (classes && tid == 0) classes[row] = arg < cols ? arg : 0;
 }
 
 // ---------------------------------------------------------------- classifier head
@@ -1024,6 +1027,7 @@ __global__ __launch_bounds__(256) void head_small_kernel(const uint16_t* __restr
       }
     }
     if (tid == 0) {
+      if (arg >= N) arg = 0;   // an all-NaN row (see softmax_argmax_kernel)
       classes[m] = arg;
       if (classes_h) classes_h[m] = arg;
     }
