@@ -207,12 +207,20 @@ class FusedConv:
         M = n * ho * wo
         args = (x, self.w, self.b, res, kh, kw, self.sh, self.sw, pt, pb, pl, pr, ACT[self.act])
         out = torch.empty((n, ho, wo, self.cout), device=x.device, dtype=BF16)
-        key = ("conv", tuple(x.shape), x.dtype, self.cout, kh, kw, self.sh, res is not None, self.act, self.post_mode)
         K = kh * 32 if self.c4 else kh * kw * self.cin
         dma = not self.c4 and self.cin % 8 == 0      # bf16 dense/im2col operands -> DMA-ring configs apply
         # pipelined cgemm kernel applies (im2col / dense with C % 64, or the padded RGBA stem)
         aligned = (dma and self.cin % 64 == 0) or self.c4
-        halo = aligned and not self.c4 and kh == 3 and kw == 3 and self.sh == 1 and self.sw == 1
+        # the halo kernel's tile origin reaches at most 2 rows / columns into the top / left padding
+        # (halo.hip halo_supported)
+        halo_shape = aligned and not self.c4 and kh == 3 and kw == 3 and self.sh == 1
+        halo = halo_shape and self.sw == 1 and pt <= 2 and pl <= 2
+        # a pick is only valid for the launches that share its candidate list: a column stride that
+        # differs from the row stride, or padding that rules the halo configs out, is part of the key
+        # (appended only then, so the keys of square-stride convs -- the committed table's -- are unchanged)
+        key = ("conv", tuple(x.shape), x.dtype, self.cout, kh, kw, self.sh, res is not None, self.act,
+               self.post_mode) + ((self.sw,) if self.sw != self.sh else ()) + \
+            (("nohalo",) if halo_shape and self.sw == 1 and not halo else ())
         kw_post, outs = _post_kwargs(self, out)
         run = lambda c, s: H.conv2d(*args, cfg=c, out=out, splits=s, **kw_post)  # noqa
         cfg, splits = tuned_config(key, M, self.cout, run, K, dma, aligned, halo=halo,
@@ -263,7 +271,8 @@ class FusedDualConv:
         h, x = _to_bf16(h).contiguous(), _to_bf16(x).contiguous()
         n, ho, wo, _ = h.shape
         out = torch.empty((n, ho, wo, self.cout), device=h.device, dtype=BF16)
-        key = ("dual", tuple(h.shape), tuple(x.shape), self.cout, self.sh, self.act, self.post_mode)
+        key = ("dual", tuple(h.shape), tuple(x.shape), self.cout, self.sh, self.act, self.post_mode) + \
+            ((self.sw,) if self.sw != self.sh else ())
         kw_post, outs = _post_kwargs(self, out)
         run = lambda c, s: H.conv2d_dual(h, x, self.w, self.b, self.sh, self.sw, ACT[self.act], c, out, s,  # noqa
                                          **kw_post)
@@ -421,7 +430,9 @@ class DeferredLNMatMul(FusedMatMul):
                                 a_st, self.colsum, self.a_ln[0] if self.a_ln else 1e-12,
                                 r_st, ra[0] if ra else None, ra[1] if ra else None, ra[2] if ra else 1e-12,
                                 self.emit)
-        cfg, _ = tuned_config(key, M, self.n, run, self.k, True, True, no_split=True, ln=True)
+        # linear_lnx takes cgemm configs only: the untimed pick (autotuning off, or under graph
+        # capture) must be one of them, not the igemm heuristic
+        cfg, _ = tuned_config(key, M, self.n, run, self.k, True, True, cgemm_only=True, no_split=True, ln=True)
         y, st = run(cfg, 1)
         return [y, st] if self.emit else [y]
 
