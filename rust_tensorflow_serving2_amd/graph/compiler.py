@@ -151,8 +151,9 @@ class Program:
         return bool(users)
 
     def op_histogram(self, flat: bool = False) -> Dict[str, int]:
-        """Steps per op; ``flat``: count the member ops of block ops (``_FlowBlock``)
-        instead of the blocks."""
+        """Steps per op; ``flat``: count the member ops of block ops (impls with
+        ``subs``: ``_FlowBlock``, the dual-source ``_ChainConv``) instead of the
+        blocks."""
         h: Dict[str, int] = {}
         for _fn, node, _i, _o in self.steps:
             subs = getattr(node.attrs.get("_impl"), "subs", None) if flat else None

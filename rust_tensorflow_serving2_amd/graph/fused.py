@@ -882,8 +882,14 @@ O.OPS["_StemPool"] = _impl_op
 # is chained in the graph and ChainConv times the chain against the two
 # convs per batch bucket (ops.tuned_choice), so each bucket runs its faster
 # form.  TFSERVE_CONV_CHAIN_SHAPES=stage1 restores the stage-1-only pass.
+#
+# CHAIN_SHAPES_DUAL: (c1 + c2, N1, N2) of the dual form, where the expand is a
+# stride-1 ``FusedDualConv`` (stage 1's projecting first block: expand conv
+# and projection shortcut as one K-concatenated GEMM over two A sources).  A
+# stage-1 shape: chained by default and kept by TFSERVE_CONV_CHAIN_SHAPES=stage1.
 CHAIN_SHAPES_ALL = {(64, 256, 64), (64, 256, 128), (128, 512, 128), (128, 512, 256)}
 CHAIN_SHAPES_STAGE1 = {(64, 256, 64), (64, 256, 128)}
+CHAIN_SHAPES_DUAL = {(128, 256, 64)}
 CHAIN_SHAPES_DEFAULT = CHAIN_SHAPES_ALL
 
 
@@ -892,25 +898,38 @@ class ChainConv:
     bottleneck's reduce 1x1 conv (+ act), which reads exactly its output, as
     one kernel (``hip().conv_chain``, kernels/chain.hip): outputs
     ``[y1, y2]``; y1 (the block output, also the next shortcut) is written
-    once and never read back by the reduce.  SURVEY.md S8 fused conv epilogues;
-    the request path is the reference client's ResNet Predict
+    once and never read back by the reduce.  ``a`` is a ``FusedConv`` (inputs
+    ``[x]`` or ``[x, residual]``) or a stride-1 ``FusedDualConv`` (inputs
+    ``[h, x]``: the kernel's two A sources, no residual).  SURVEY.md S8 fused
+    conv epilogues; the request path is the reference client's ResNet Predict
     (/root/reference/src/lib.rs:229-257)."""
 
     children = ("a", "b")
 
-    def __init__(self, a: FusedConv, b: FusedConv):
+    def __init__(self, a, b: FusedConv):
         self.a, self.b = a, b
+        self.dual = isinstance(a, FusedDualConv)
         self.use_hip = a.use_hip and b.use_hip
         self.name = a.name
+        if self.dual:
+            # three convs in one op (expand + projection shortcut + next
+            # reduce): a flat op histogram (Program.op_histogram(flat=True),
+            # which counts convs as 2 per dual conv and 2 per chain) lists the
+            # two member ops, each of which runs as itself when the tuned
+            # choice is 0; the plain histogram lists the _ChainConv
+            from types import SimpleNamespace
+            self.subs = [(a, SimpleNamespace(op="_FusedDualConv")), (b, SimpleNamespace(op="_FusedConv2D"))]
 
     def __call__(self, ctx, node, ins):
         x = O.to_torch(ins[0])
-        res = O.to_torch(ins[1]) if len(ins) > 1 else None
         a, b = self.a, self.b
 
         def split():
             y1 = a(ctx, node, ins)[0]
             return [y1, b(ctx, node, [y1])[0]]
+        if self.dual:
+            return self._call_dual(x, O.to_torch(ins[1]), split)
+        res = O.to_torch(ins[1]) if len(ins) > 1 else None
         if not (self.use_hip and x.is_cuda and x.dim() == 4 and x.shape[-1] == a.cin):
             return split()
         from ..ops import ACT, hip, tuned_choice
@@ -929,6 +948,23 @@ class ChainConv:
         # (N1 = 512) chains measured no faster than two convs at b32
         # (round-5 ADVICE)
         dflt = 1 if (a.cin, a.cout, b.cout) in CHAIN_SHAPES_STAGE1 else 0
+        pick = tuned_choice(key, {1: chained, 0: split}, default=dflt)
+        return chained() if pick == 1 else split()
+
+    def _call_dual(self, h, x, split):
+        a, b = self.a, self.b
+        if not (self.use_hip and h.is_cuda and h.dim() == 4 and x.dim() == 4 and h.shape[:3] == x.shape[:3] and
+                h.shape[-1] == a.c1 and x.shape[-1] == a.c2):
+            return split()
+        from ..ops import ACT, hip, tuned_choice
+        hb, xb = _to_bf16(h).contiguous(), _to_bf16(x).contiguous()
+
+        def chained():
+            return list(hip().conv_chain(hb, a.w, a.b, None, ACT[a.act], b.w, b.b, ACT[b.act], x2=xb))
+        # the shortcut element (a plain chain's "has a residual" flag) names the
+        # second source: this key differs from a plain chain's over the same h
+        key = ("chain", tuple(h.shape), a.cout, b.cout, ("dual", a.c2), a.act, b.act)
+        dflt = 1 if (a.c1 + a.c2, a.cout, b.cout) in CHAIN_SHAPES_DUAL else 0
         pick = tuned_choice(key, {1: chained, 0: split}, default=dflt)
         return chained() if pick == 1 else split()
 
@@ -1342,7 +1378,9 @@ def fuse_conv_chain(g, order, fed, fetch_refs, device, opts):
     """``_FusedConv2D`` A (1x1 expand, optional residual) whose output feeds a
     ``_FusedConv2D`` B (1x1 reduce, no residual) -> ``_ChainConv`` with outputs
     ``[A, B]`` when (A.cin, A.cout, B.cout) is a kernel shape; A's other
-    consumers (the next shortcut) keep reading output 0.  GPU programs only
+    consumers (the next shortcut) keep reading output 0.  A may also be a
+    stride-1 ``_FusedDualConv`` without a post output (inputs ``[h, x]``,
+    shape (c1 + c2, cout, B.cout) in CHAIN_SHAPES_DUAL).  GPU programs only
     (``TFSERVE_CONV_CHAIN=0`` disables it, ``force`` applies it on CPU too:
     the op then runs both reference convs)."""
     import os
@@ -1353,10 +1391,14 @@ def fuse_conv_chain(g, order, fed, fetch_refs, device, opts):
         return
     for name in order:
         p = g.nodes.get(name)
-        if p is None or p.op != "_FusedConv2D" or name in c.fetch_nodes:
+        if p is None or p.op not in ("_FusedConv2D", "_FusedDualConv") or name in c.fetch_nodes:
             continue
         a = p.attrs["_impl"]
-        if not _chainable_1x1(a):
+        dual = p.op == "_FusedDualConv"
+        if dual:
+            if not (a.use_hip and a.sh == a.sw == 1 and a.post is None and a.act in ("relu", "none")):
+                continue
+        elif not _chainable_1x1(a):
             continue
         cons = c.cons.get(name, [])
         if any(i != 0 for _c, _p, i in cons):
@@ -1368,7 +1410,8 @@ def fuse_conv_chain(g, order, fed, fetch_refs, device, opts):
             continue
         bnode = bs[0]
         b = bnode.attrs["_impl"]
-        if b.cin != a.cout or (a.cin, a.cout, b.cout) not in shapes:
+        shape = (a.c1 + a.c2 if dual else a.cin, a.cout, b.cout)
+        if b.cin != a.cout or shape not in (CHAIN_SHAPES_DUAL if dual else shapes):
             continue
         chain = ChainConv(a, b)
         p.op = "_ChainConv"

@@ -12,6 +12,12 @@
 // written once and never read back.  Stage-1/2 shapes: K1 in {64, 128},
 // N1 in {256, 512}, N2 in {64, 128, 256}.
 //
+// Dual form (<128, 256, 64, DUAL>, stage 1's projecting first block): X is two
+// dense sources, X = [Xa | Xb] with Xa [M][K1a] and Xb [M][K1 - K1a] (the
+// expand conv's input and the stride-1 projection shortcut's input), W1 the
+// K-concatenated [N1][K1] matrix; a 64-channel k-tile lies wholly in one
+// source, so only the phase-1 A DMAs differ.  No residual there (R = nullptr).
+//
 //   * phase 1: X tile [64][K1] and all of W1 [N1][K1] land in LDS by direct
 //     DMA (buffer_load ... lds, 16-B chunks XOR-swizzled by row & 7), the
 //     residual chunks and biases this lane will need are loaded into registers
@@ -33,7 +39,8 @@ namespace {
 using namespace gemm;
 
 struct ChainArgs {
-  const uint16_t* x;     // [M][K1] bf16
+  const uint16_t* x;     // [M][K1] bf16 ([M][K1a] in the dual form)
+  const uint16_t* x2;    // dual form: [M][K1 - K1a] bf16, the k-tiles from K1a on
   const uint16_t* w1;    // [N1][ldw1] bf16
   const float* b1;       // [N1]
   const uint16_t* res;   // [M][N1] bf16 or nullptr
@@ -42,6 +49,7 @@ struct ChainArgs {
   const float* b2;       // [N2]
   uint16_t* y2;          // [M][N2] bf16
   int M, ldw1, ldw2;
+  int K1a;               // dual form: channels of x (a multiple of KT)
   float lo1, lo2;        // activation floors: 0 (ReLU) or -inf (none)
 };
 
@@ -71,7 +79,7 @@ struct CH {
   static_assert((S2 - 2) * W2PW < 64, "vmcnt range");
 };
 
-template <int K1, int N1, int N2>
+template <int K1, int N1, int N2, bool DUAL = false>
 __global__ __launch_bounds__(256, 1) void conv_chain_kernel(ChainArgs p) {
   using G = CH<K1, N1, N2>;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -84,8 +92,12 @@ __global__ __launch_bounds__(256, 1) void conv_chain_kernel(ChainArgs p) {
   const int m0 = xcd_remap(blockIdx.x, gridDim.x) * kBM;
   const int M = p.M;
 
+  // dual form: x holds channels [0, K1a) and x2 the rest, both dense rows
+  const int Ka = DUAL ? p.K1a : K1;
   const __amdgpu_buffer_rsrc_t rsX = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<uint16_t*>(p.x), 0, int(long(M) * K1 * 2), 0x00020000);
+      const_cast<uint16_t*>(p.x), 0, int(long(M) * Ka * 2), 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsX2 = __builtin_amdgcn_make_buffer_rsrc(
+      const_cast<uint16_t*>(DUAL ? p.x2 : p.x), 0, DUAL ? int(long(M) * (K1 - Ka) * 2) : 0, 0x00020000);
   const __amdgpu_buffer_rsrc_t rsW1 = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<uint16_t*>(p.w1), 0, int(long(N1) * p.ldw1 * 2), 0x00020000);
   const __amdgpu_buffer_rsrc_t rsW2 = __builtin_amdgcn_make_buffer_rsrc(
@@ -98,8 +110,14 @@ __global__ __launch_bounds__(256, 1) void conv_chain_kernel(ChainArgs p) {
     const int q = wid * G::APW + j;                 // over KT1 x 8 pieces
     const int kt = q / (kBM / 8), pc = q % (kBM / 8);
     const int m = m0 + pc * 8 + prow;
-    const uint32_t v = m < M ? (uint32_t(m) * K1 + uint32_t(kt * KT) + kc) * 2u : kOOB;
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsX, (lds_ptr_t)(smem + kt * kBM * KT * 2 + pc * 1024), 16, v, 0, 0, 0);
+    if (DUAL && kt * KT >= Ka) {   // a k-tile lies wholly in one source (wave-uniform: kt follows wid)
+      const uint32_t v = m < M ? (uint32_t(m) * uint32_t(K1 - Ka) + uint32_t(kt * KT - Ka) + kc) * 2u : kOOB;
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsX2, (lds_ptr_t)(smem + kt * kBM * KT * 2 + pc * 1024), 16, v, 0, 0,
+                                               0);
+    } else {
+      const uint32_t v = m < M ? (uint32_t(m) * uint32_t(Ka) + uint32_t(kt * KT) + kc) * 2u : kOOB;
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsX, (lds_ptr_t)(smem + kt * kBM * KT * 2 + pc * 1024), 16, v, 0, 0, 0);
+    }
   }
 #pragma unroll
   for (int j = 0; j < G::W1PW; ++j) {
@@ -330,31 +348,37 @@ __global__ __launch_bounds__(256, 1) void conv_chain_kernel(ChainArgs p) {
   }
 }
 
-template <int K1, int N1, int N2>
+template <int K1, int N1, int N2, bool DUAL = false>
 hipError_t launch_chain(const ChainArgs& a, hipStream_t s) {
   using G = CH<K1, N1, N2>;
-  hipError_t e = ensure_dyn_lds(reinterpret_cast<const void*>(&conv_chain_kernel<K1, N1, N2>), G::LDS);
+  hipError_t e = ensure_dyn_lds(reinterpret_cast<const void*>(&conv_chain_kernel<K1, N1, N2, DUAL>), G::LDS);
   if (e != hipSuccess) return e;
   const int tiles = (a.M + kBM - 1) / kBM;
-  hipLaunchKernelGGL((conv_chain_kernel<K1, N1, N2>), dim3(tiles), dim3(kNT), G::LDS, s, a);
+  hipLaunchKernelGGL((conv_chain_kernel<K1, N1, N2, DUAL>), dim3(tiles), dim3(kNT), G::LDS, s, a);
   return hipGetLastError();
 }
 
 }  // namespace
 
-bool conv_chain_supported(int K1, int N1, int N2) {
+bool conv_chain_supported(int K1, int N1, int N2, bool dual) {
+  // dual form: K1 = both sources' channels; 80 KB of LDS like the other stage-1 shapes
+  static_assert(CH<128, 256, 64>::LDS <= 80 * 1024, "two workgroups per CU");
+  if (dual) return K1 == 128 && N1 == 256 && N2 == 64;
   return (K1 == 64 && N1 == 256 && (N2 == 64 || N2 == 128)) || (K1 == 128 && N1 == 512 && (N2 == 128 || N2 == 256));
 }
 
 hipError_t conv_chain_launch(const uint16_t* x, const uint16_t* w1, int ldw1, const float* b1, const uint16_t* res,
                              uint16_t* y1, const uint16_t* w2, int ldw2, const float* b2, uint16_t* y2, int M, int K1,
-                             int N1, int N2, int act1, int act2, hipStream_t s) {
+                             int N1, int N2, int act1, int act2, hipStream_t s, const uint16_t* x2, int K1a) {
   if (M <= 0) return hipSuccess;
-  if (!conv_chain_supported(K1, N1, N2) || ldw1 < K1 || ldw1 % 8 || ldw2 < N1 || ldw2 % 8) return hipErrorInvalidValue;
+  const bool dual = x2 != nullptr;
+  if (dual && (K1a <= 0 || K1a >= K1 || K1a % KT || (K1 - K1a) % KT)) return hipErrorInvalidValue;
+  if (!conv_chain_supported(K1, N1, N2, dual) || ldw1 < K1 || ldw1 % 8 || ldw2 < N1 || ldw2 % 8) return hipErrorInvalidValue;
   if ((act1 != kActNone && act1 != kActRelu) || (act2 != kActNone && act2 != kActRelu)) return hipErrorInvalidValue;
   if (long(M) * N1 * 2 >= 0x7fffffffL) return hipErrorInvalidValue;   // 32-bit buffer offsets
-  ChainArgs a{x, w1, b1, res, y1, w2, b2, y2, M, ldw1, ldw2, act1 == kActRelu ? 0.f : -INFINITY,
+  ChainArgs a{x, x2, w1, b1, res, y1, w2, b2, y2, M, ldw1, ldw2, dual ? K1a : K1, act1 == kActRelu ? 0.f : -INFINITY,
               act2 == kActRelu ? 0.f : -INFINITY};
+  if (dual) return launch_chain<128, 256, 64, true>(a, s);
   if (K1 == 64 && N1 == 256 && N2 == 64) return launch_chain<64, 256, 64>(a, s);
   if (K1 == 64 && N1 == 256 && N2 == 128) return launch_chain<64, 256, 128>(a, s);
   if (K1 == 128 && N1 == 512 && N2 == 128) return launch_chain<128, 512, 128>(a, s);

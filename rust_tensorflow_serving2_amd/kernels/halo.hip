@@ -463,6 +463,11 @@ __global__ __launch_bounds__(64 * WGM * WGN) void halo_conv_kernel(IGemmArgs p) 
 //   * raw s_barrier (lds_barrier) only: a __syncthreads() would drain vmcnt.
 // Plain bf16 output only (bias, act != erf; no residual / second output /
 // split): the launcher rejects the rest, which the tuner skips.
+// Trace stamps (scripts/wg_trace.py --persist): 0 entry, 1 filter + first halo
+// landed, 2 tile 0 after its K loop, 3 tile 0's stores issued, 4 tile 1 past
+// its opening wait, 5 tile 1 after its K loop, 6 exit (stores drained).  They
+// are compiled into the TRACE instance only, which the launcher picks when a
+// trace buffer is set: the production instance carries none of their branches.
 constexpr int kPersistBM = 128, kPersistBN = 64, kPersistHR = 192;
 struct HPs {
   static constexpr int BM = kPersistBM, BN = kPersistBN, HR = kPersistHR;
@@ -479,6 +484,7 @@ struct HPs {
   static_assert(LDS <= 160 * 1024, "LDS budget");
 };
 
+template <bool TRACE>
 __global__ __launch_bounds__(512, 1) void halo_persist_kernel(IGemmArgs p, int ntiles) {
   using G = HPs;
   constexpr int BM = G::BM, BN = G::BN;
@@ -496,6 +502,7 @@ __global__ __launch_bounds__(512, 1) void halo_persist_kernel(IGemmArgs p, int n
   const int wm = wid / G::WGN, wn = wid % G::WGN;
   const int prow = lane >> 3;
   const int fr = lane & 15, fq = lane >> 4;
+  if constexpr (TRACE) trace_stamp(p, 0);
 
   const __amdgpu_buffer_rsrc_t rsA =
       __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.a), 0, int(p.a_bytes), 0x00020000);
@@ -575,6 +582,8 @@ __global__ __launch_bounds__(512, 1) void halo_persist_kernel(IGemmArgs p, int n
     if (k == 0) gemm::wait_vmcnt<0>();
     else gemm::wait_vmcnt<G::kStores>();
     gemm::lds_barrier();   // every wave's DMAs landed; halo buffer b^1 and the staging tile are read-free
+    if constexpr (TRACE)
+      if (k < 2) trace_stamp(p, k == 0 ? 1 : 4);
     const int tn = t + gridDim.x;
     if (tn < ntiles) issue_halo(tn, b ^ 1);
     __builtin_amdgcn_sched_barrier(0);
@@ -624,6 +633,8 @@ __global__ __launch_bounds__(512, 1) void halo_persist_kernel(IGemmArgs p, int n
             acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f.a[kk][i], f.b[kk][j], acc[i][j], 0, 0, 0);
     }
     __builtin_amdgcn_sched_barrier(0);
+    if constexpr (TRACE)
+      if (k < 2) trace_stamp(p, k == 0 ? 2 : 5);
 
     // ---- epilogue: bias + act -> bf16 staging -> 16-B buffer stores
     auto stage = [&](auto act_tag) __attribute__((always_inline)) {
@@ -668,8 +679,11 @@ __global__ __launch_bounds__(512, 1) void halo_persist_kernel(IGemmArgs p, int n
         __builtin_amdgcn_raw_buffer_store_b128(v, rsO, off, 0, 0);
       }
     }
+    if constexpr (TRACE)
+      if (k == 0) trace_stamp(p, 3);
   }
   gemm::wait_vmcnt<0>();
+  if constexpr (TRACE) trace_stamp(p, 6);
 }
 
 // (the ping-pong halo kernel, ids 144/145, was removed in round 6: 0 picks in
@@ -761,9 +775,15 @@ hipError_t launch_halo_persist(const IGemmArgs& a0, hipStream_t s) {
     cus = n;
   }
   const int grid = int(tiles < cus ? tiles : cus);
-  hipError_t e = ensure_dyn_lds(reinterpret_cast<const void*>(&halo_persist_kernel), G::LDS);
+  if (a.trace != nullptr) {
+    hipError_t e = ensure_dyn_lds(reinterpret_cast<const void*>(&halo_persist_kernel<true>), G::LDS);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(halo_persist_kernel<true>, dim3(unsigned(grid)), dim3(G::NT), G::LDS, s, a, int(tiles));
+    return hipGetLastError();
+  }
+  hipError_t e = ensure_dyn_lds(reinterpret_cast<const void*>(&halo_persist_kernel<false>), G::LDS);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(halo_persist_kernel, dim3(unsigned(grid)), dim3(G::NT), G::LDS, s, a, int(tiles));
+  hipLaunchKernelGGL(halo_persist_kernel<false>, dim3(unsigned(grid)), dim3(G::NT), G::LDS, s, a, int(tiles));
   return hipGetLastError();
 }
 

@@ -153,11 +153,15 @@ hipError_t stem_pool_launch(const void* x, bool x_bf16, const uint16_t* w, int l
                             int Hp, int Wp, int act, const float* pscale, const float* pshift, int pact,
                             hipStream_t s);
 // Two chained 1x1 convs in one launch (chain.hip): y1 = act1(x w1^T + b1 + res),
-// y2 = act2(y1 w2^T + b2); (K1, N1, N2) in conv_chain_supported().
-bool conv_chain_supported(int K1, int N1, int N2);
+// y2 = act2(y1 w2^T + b2); (K1, N1, N2) in conv_chain_supported().  Dual form
+// (x2 != nullptr): the rows of the first GEMM's A are [x | x2], x [M][K1a] and
+// x2 [M][K1 - K1a] (a bottleneck's expand conv and its stride-1 projection
+// shortcut as one K-concatenated GEMM); w1 is [N1][>= K1] over both.
+bool conv_chain_supported(int K1, int N1, int N2, bool dual = false);
 hipError_t conv_chain_launch(const uint16_t* x, const uint16_t* w1, int ldw1, const float* b1, const uint16_t* res,
                              uint16_t* y1, const uint16_t* w2, int ldw2, const float* b2, uint16_t* y2, int M, int K1,
-                             int N1, int N2, int act1, int act2, hipStream_t s);
+                             int N1, int N2, int act1, int act2, hipStream_t s, const uint16_t* x2 = nullptr,
+                             int K1a = 0);
 // NHWC bf16 max-pool (TF SAME/VALID padding given explicitly).  With `scale`
 // (and `shift`): y = act(max * scale[c] + shift[c]) — a folded inference
 // BatchNorm (+ ReLU when act == 1) applied after the pooling.

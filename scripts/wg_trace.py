@@ -8,6 +8,11 @@ and the median / p90 of each phase.
 
     python scripts/wg_trace.py --layers s1_3x3 s3_3x3 s3_1x1_in --cfgs 48:1 51:1 42:1
 
+``--persist`` traces the persistent 3x3 kernel (kernels/halo.hip
+halo_persist_kernel, config 146) with its own stamps: the first tile's phases
+and the second tile's opening wait, which shows whether the one-tile halo
+prefetch covers the HBM round trip.
+
 Operands rotate over 8 copies (as scripts/conv_sweep.py): the traced launch
 finds its input in the Infinity Cache, not in L2 -- what a layer sees in the
 serving graph after its producer ran.
@@ -41,9 +46,20 @@ def main():
     ap.add_argument("--gemm", nargs="*", default=[], help="dense GEMMs MxNxK (hip().linear) instead of conv layers")
     ap.add_argument("--attention", nargs="*", default=[],
                     help="fixed-S attention BxSxH (D = 64, key mask): stamps entry / staged / softmax / PV / stored")
+    ap.add_argument("--persist", action="store_true",
+                    help="halo_persist_kernel (config 146) on the s1_3x3 layer: per-tile phases")
     a = ap.parse_args()
     n = a.batch
     H = hip()
+    if a.persist:
+        h, cin, cout, k, s, _resid = LAYERS["s1_3x3"]
+        xs = [torch.randn(n, h, h, cin, device="cuda").to(BF) for _ in range(8)]
+        ws = [(torch.randn(cout, k * k * cin, device="cuda") * 0.05).to(BF) for _ in range(8)]
+        outs = [torch.empty(n, h, h, cout, device="cuda", dtype=BF) for _ in range(8)]
+        b = torch.zeros(cout, device="cuda")
+        persist_report("s1_3x3", lambda j: H.conv2d(xs[j], ws[j], b, None, k, k, s, s, 1, 1, 1, 1, ACT["relu"], 146,
+                                                    outs[j], False, 1))
+        return
     for shape in a.attention:
         B, S, NH = (int(v) for v in shape.split("x"))
         qkvs = [torch.randn(B, S, 3 * NH * 64, device="cuda").to(BF) for _ in range(8)]
@@ -112,6 +128,44 @@ def attention_report(name, run):
                       "span_us": round(float((t[:, 4].max() - t0) * TICK_US), 2), "cus": len(per_cu),
                       "max_wg_per_cu": max(per_cu.values()),
                       **{k: {"p50": round(q(v, .5), 2), "p90": round(q(v, .9), 2), "max": round(max(v), 2)}
+                         for k, v in ph.items()}}), flush=True)
+
+
+def persist_report(name, run):
+    """Phases of halo_persist_kernel (kernels/halo.hip stamps 0..6): workgroups
+    that walk at least two tiles have all seven."""
+    H = hip()
+    for j in range(8):
+        run(j)
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    for j in range(7):
+        run(j)
+    e0.record()
+    run(7)
+    e1.record()
+    e1.synchronize()
+    ev_us = e0.elapsed_time(e1) * 1e3
+    tr = torch.zeros(1 << 12, 8, dtype=torch.int64, device="cuda")
+    for j in range(7):
+        run(j)
+    H.set_wg_trace(tr)
+    run(7)
+    H.set_wg_trace(None)
+    torch.cuda.synchronize()
+    t = tr.cpu()
+    t = t[t[:, 0] > 0]
+    nwg = int(t.shape[0])
+    t0 = int(t[:, 0].min())
+    span = float((t[:, 6].max() - t0) * TICK_US)
+    t = t[t[:, 4] > 0]
+    ph = {"start": t[:, 0] - t0, "first_data": t[:, 1] - t[:, 0], "tile0_kloop": t[:, 2] - t[:, 1],
+          "tile0_epilogue": t[:, 3] - t[:, 2], "tile1_opening_wait": t[:, 4] - t[:, 3],
+          "tile1_kloop": t[:, 5] - t[:, 4], "rest": t[:, 6] - t[:, 5], "life": t[:, 6] - t[:, 0]}
+    ph = {k: (v.double() * TICK_US).tolist() for k, v in ph.items()}
+    print(json.dumps({"layer": name, "cfg": 146, "workgroups": nwg, "two_tile_workgroups": int(t.shape[0]),
+                      "event_us": round(ev_us, 2), "span_us": round(span, 2),
+                      **{k + "_us": {"p50": round(q(v, .5), 2), "p90": round(q(v, .9), 2), "max": round(max(v), 2)}
                          for k, v in ph.items()}}), flush=True)
 
 
