@@ -981,6 +981,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     v.push_back(tfsk::kHaloPersistCfg);
     return v;
   });
+  m.def("halo_persist_tiles", [](int64_t n, int64_t ho, int64_t wo) {
+    long tiles = 0;
+    int th = 0, tw = 0, ti = 0;
+    TORCH_CHECK(n > 0 && ho > 0 && wo > 0 && n * ho * wo < (int64_t(1) << 23) &&
+                    tfsk::halo_persist_tiles(int(n), int(ho), int(wo), tiles, th, tw, ti),
+                "halo_persist_tiles: no persistent launch for ", n, " x ", ho, " x ", wo);
+    return std::make_tuple(int64_t(tiles), th, tw, ti);
+  }, py::arg("n"), py::arg("ho"), py::arg("wo"),
+     "(tiles, TH, TW, TI) of config 146's launch for n images of ho x wo outputs (host only; launches nothing)");
   m.def("config_tile", [](int cfg) {
     if (is_halo_cfg(cfg)) return std::make_pair(tfsk::halo_config_bm(cfg), tfsk::halo_config_bn(cfg));
     if (is_cgemm_cfg(cfg)) return std::make_pair(tfsk::cgemm_config_bm(cfg), tfsk::cgemm_config_bn(cfg));

@@ -69,6 +69,10 @@ inline bool halo_cfg_id(int cfg) {
   return (cfg >= kHaloCfgBase && cfg < kHaloCfgBase + kNumHaloConfigs) || cfg == kHaloPersistCfg ||
          (cfg >= kHaloPfCfgBase && cfg < kHaloPfCfgBase + kNumHaloConfigs && cfg != kHaloPfCfgBase + kHaloPfMissing);
 }
+// host-only, launches nothing: the tile walk the persistent kernel's launcher
+// uses for n images of ho x wo output pixels (tiles of ti images x th x tw
+// pixels; the grid is min(tiles, CUs)).  false: no such launch.
+bool halo_persist_tiles(int n, int ho, int wo, long& tiles, int& th, int& tw, int& ti);
 bool halo_supported(const IGemmArgs& a);
 int halo_config_bm(int cfg);
 int halo_config_bn(int cfg);

@@ -751,6 +751,16 @@ hipError_t launch_halo_cfg(const IGemmArgs& a0, hipStream_t s) {
   return hipGetLastError();
 }
 
+// The persistent kernel's tile walk for a.M rows of Ho x Wo outputs: sets
+// a.TH / a.TW / a.TI and returns the tile count (-1: no block fits).  The
+// launcher and the host-side query (halo_persist_tiles) both go through it.
+long persist_geometry(IGemmArgs& a) {
+  if (!pick_block(a.Ho, a.Wo, kPersistBM, kPersistHR, a.TH, a.TW)) return -1;
+  a.TI = pick_images(a, kPersistBM, kPersistHR);
+  const int nimg = a.M / (a.Ho * a.Wo);
+  return long((nimg + a.TI - 1) / a.TI) * ((a.Ho + a.TH - 1) / a.TH) * ((a.Wo + a.TW - 1) / a.TW);
+}
+
 hipError_t launch_halo_persist(const IGemmArgs& a0, hipStream_t s) {
   using G = HPs;
   IGemmArgs a = a0;
@@ -760,10 +770,8 @@ hipError_t launch_halo_persist(const IGemmArgs& a0, hipStream_t s) {
       a.out == nullptr || a.act == kActGeluErf || epi_f32_env() || a.counters != nullptr || a.ldc % 8)
     return hipErrorInvalidValue;
   if (long(a.M) * a.ldc * 2 >= 0x7fffffffL) return hipErrorInvalidValue;
-  if (!pick_block(a.Ho, a.Wo, G::BM, G::HR, a.TH, a.TW)) return hipErrorInvalidValue;
-  a.TI = pick_images(a, G::BM, G::HR);
-  const int nimg = a.M / (a.Ho * a.Wo);
-  const long tiles = long((nimg + a.TI - 1) / a.TI) * ((a.Ho + a.TH - 1) / a.TH) * ((a.Wo + a.TW - 1) / a.TW);
+  const long tiles = persist_geometry(a);
+  if (tiles < 0) return hipErrorInvalidValue;
   if (tiles == 0) return hipSuccess;
   if (tiles >= (1L << 30)) return hipErrorInvalidValue;
   static int cus = 0;
@@ -811,6 +819,19 @@ long halo_tiles(const IGemmArgs& a0, int cfg) {
   const int ti = pick_images(a, kHBM[c], kHHR[c]);
   return long((nimg + ti - 1) / ti) * ((a.Ho + a.TH - 1) / a.TH) * ((a.Wo + a.TW - 1) / a.TW) *
          ((a.N + kHBN[c] - 1) / kHBN[c]);
+}
+
+bool halo_persist_tiles(int n, int ho, int wo, long& tiles, int& th, int& tw, int& ti) {
+  if (n <= 0 || ho <= 0 || wo <= 0 || long(n) * ho * wo >= (1L << 23)) return false;
+  IGemmArgs a{};
+  a.Ho = ho;
+  a.Wo = wo;
+  a.M = n * ho * wo;
+  tiles = persist_geometry(a);
+  th = a.TH;
+  tw = a.TW;
+  ti = a.TI;
+  return tiles > 0;
 }
 
 bool halo_supported(const IGemmArgs& a) {

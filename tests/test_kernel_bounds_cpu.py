@@ -212,6 +212,79 @@ def test_conv_ideal_within_bound_and_mutants_rejected(case):
     rejected(bf_round(torch.relu(v * sc)), ref2, bound2)
 
 
+# ------------------------------------------------------------------ many-tile launch geometries
+# The shapes of test_launch_geometry_gpu.py.  A wrong tile walk or a tile remap
+# that is no bijection leaves whole tiles unwritten, stale or exchanged; the
+# mutants below are those, on 128-row tiles of the flattened [M, N] output.
+def test_nan_against_finite_reference_is_a_violation_with_its_index():
+    ref = rnd(6, 9, seed=1).double()
+    y = ref.clone()
+    y[4, 7] = float("nan")
+    with pytest.raises(AssertionError) as e:
+        kb.assert_within(y, ref, 1e30, "unwritten")
+    assert "1 of 54" in str(e.value) and "(4, 7)" in str(e.value) and "inf" in str(e.value)
+    rejected(torch.full((6, 9), float("nan"), dtype=BF), ref, 1e30)
+    rejected(torch.full((6, 9), float("inf")), ref, 1e30)
+
+
+def tile_mutants(y, bm=128, grid=8):
+    """(name, mutated copy) of a [M, N] output computed in bm-row tiles by a
+    grid of `grid` persistent workgroups."""
+    m = y.shape[0]
+    tiles = -(-m // bm)
+    assert tiles > grid + 2
+    t = tiles // 2 + grid                      # an interior tile with a predecessor `grid` positions earlier
+
+    def rows(i):
+        return slice(i * bm, min((i + 1) * bm, m))
+    nan, zero, stale, swapped = y.clone(), y.clone(), y.clone(), y.clone()
+    nan[rows(t)] = float("nan")
+    zero[rows(t)] = 0
+    stale[rows(t)] = y[rows(t - grid)]
+    swapped[rows(t)], swapped[rows(t - 1)] = y[rows(t - 1)], y[rows(t)]
+    return [("a tile left as NaN", nan), ("a tile left as zeros", zero),
+            ("a tile holding the tile gridDim positions earlier", stale), ("two tiles swapped", swapped)]
+
+
+# 1a at the 256 CUs of an MI355X (tiles == CUs, CUs + 1, 2 CUs + 3), both pad sets; 1b: the 11-image conv with
+# Cout 72 / 200, stride 2 and the asymmetric pads, and the halo family's 128-channel split case
+GEOMETRY_CONVS = ([(n, ho + 2 - p[0] - p[1], wo + 2 - p[2] - p[3], 64, 64, 3, 1, p)
+                   for n, ho, wo in ((128, 16, 16), (513, 7, 7), (103, 24, 24)) for p in ((1, 1, 1, 1), (0, 2, 1, 0))]
+                  + [(11, 24, 24, 64, 72, 3, 1, (1, 1, 1, 1)), (11, 24, 24, 64, 200, 3, 1, (1, 1, 1, 1)),
+                     (11, 47, 47, 64, 72, 3, 2, (1, 1, 1, 1)), (11, 24, 24, 64, 200, 3, 1, (0, 2, 1, 0)),
+                     (11, 24, 24, 128, 72, 3, 1, (1, 1, 1, 1))])
+
+
+@pytest.mark.parametrize("case", GEOMETRY_CONVS)
+def test_geometry_conv_ideal_within_bound_and_tile_mutants_rejected(case):
+    n, h, w, cin, cout, k, s, pads = case
+    x, wt, b, r = kb.conv_inputs(*case)
+    res = None if cout == 64 else r                            # (the persistent kernel takes no residual)
+    pre, mag = kb.conv_parts(x, wt, b, s, pads, res)
+    for act in ("none", "relu"):
+        y = ideal_conv(x, wt, b, res, s, pads, act)
+        for splits in (1, 3):
+            ref, bound = kb.epilogue(pre, mag, k * k * cin, splits, act, False)
+            assert kb.assert_within(y, ref, bound, f"conv {act}") <= 1.0
+        for name, bad in tile_mutants(y.reshape(-1, cout)):
+            rejected(bad.reshape(y.shape), ref, bound, f"{case} {act}: {name}")
+
+
+def test_geometry_linear_ideal_within_bound_and_tile_mutants_rejected():
+    m, n, k = 6336 + 5, 200, 2880
+    x, w, b, r = kb.gemm_inputs(m, n, k)
+    pre, mag = kb.gemm_parts(x, w, b, r)
+    for act, out_f32, splits in (("relu", False, 1), ("gelu_tanh", False, 3), ("none", True, 1), ("tanh", True, 3)):
+        ref, bound = kb.epilogue(pre, mag, k, splits, act, out_f32)
+        y = ideal_gemm(x, w, b, r, act, out_f32)
+        assert kb.assert_within(y, ref, bound, f"{act} f32={out_f32}") <= 1.0
+        for name, bad in tile_mutants(y):
+            rejected(bad, ref, bound, f"linear {act} f32={out_f32}: {name}")
+        short = y.clone()                                      # the 5-row M tail never written
+        short[m - 5:] = float("nan")
+        rejected(short, ref, bound, "M tail unwritten")
+
+
 # ------------------------------------------------------------------ chain / head (bf16 intermediates)
 @pytest.mark.parametrize("k1,n1,n2,m", [(64, 256, 64, 77), (128, 512, 256, 200)])
 def test_chain_two_step_check(k1, n1, n2, m):
