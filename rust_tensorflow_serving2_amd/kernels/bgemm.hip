@@ -428,14 +428,15 @@ hipError_t launch_bg(const IGemmArgs& a0, hipStream_t s) {
 
 }  // namespace
 
-hipError_t bgemm_launch(const IGemmArgs& a, int a_mode, int idx, hipStream_t s) {
+hipError_t bgemm_launch(const IGemmArgs& a, int a_mode, int cfg, hipStream_t s) {
   if (a_mode != kADense) return hipErrorInvalidValue;     // dense operands only
   if (a.counters != nullptr) return hipErrorInvalidValue; // no in-kernel split-K fixup
   if (a.st_out != nullptr || a.a_st != nullptr || a.r_st != nullptr) return hipErrorInvalidValue;   // no deferred LN
-  switch (idx) {
-    case 0: return launch_bg<256, 256>(a, s);
-    case 1: return launch_bg<256, 128>(a, s);
-    case 2: return launch_bg<256, 192>(a, s);
+  switch (cfg) {
+#define TFSK_CASE(id, BM, BN) \
+  case id: return launch_bg<BM, BN>(a, s);
+    TFSK_BGEMM_CONFIGS(TFSK_CASE)
+#undef TFSK_CASE
     default: return hipErrorInvalidValue;
   }
 }

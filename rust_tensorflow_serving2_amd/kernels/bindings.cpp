@@ -26,16 +26,14 @@ void check(hipError_t e, const char* what) {
 }
 
 // Launch with optional split-K: raw fp32 slabs in a workspace + reduce/epilogue kernel.
-// cfg < kNumIGemmConfigs: igemm.hip (any operand mode); cfg in [kCGemmCfgBase,
-// kCGemmCfgBase + kNumCGemmConfigs): the pipelined cgemm.hip kernel (64-aligned operands).
-bool is_cgemm_cfg(int64_t cfg) {
-  return cfg >= 0 && cfg < (1 << 20) && tfsk::cgemm_cfg_id(int(cfg));
+// `cfg` is a row of tile_configs.h: an igemm.hip config (any operand mode), a
+// cgemm one (the pipelined kernels, 64-aligned operands) or a halo one (the
+// halo-tiled 3x3 stride-1 conv).  nullptr: not a config.
+const tfsk::TileConfig* config_of(int64_t cfg) {
+  return cfg >= 0 && cfg < tfsk::kTileIdEnd ? tfsk::tile_config(int(cfg)) : nullptr;
 }
-
-// halo-tiled 3x3 stride-1 conv configs (halo.hip)
-bool is_halo_cfg(int64_t cfg) {
-  return cfg >= 0 && cfg < (1 << 20) && tfsk::halo_cfg_id(int(cfg));
-}
+bool is_cgemm_cfg(int64_t cfg) { return config_of(cfg) != nullptr && tfsk::cgemm_family(config_of(cfg)->family); }
+bool is_halo_cfg(int64_t cfg) { return config_of(cfg) != nullptr && tfsk::halo_family(config_of(cfg)->family); }
 
 hipError_t launch_any(const tfsk::IGemmArgs& a, int a_mode, int64_t cfg, hipStream_t st) {
   if (is_halo_cfg(cfg)) return tfsk::halo_launch(a, int(cfg), st);
@@ -73,8 +71,7 @@ int g_trace_cap = 0;
 void run_igemm(tfsk::IGemmArgs& a, int a_mode, int64_t cfg, int64_t splits, const Tensor& like, hipStream_t st) {
   a.trace = g_trace;
   a.trace_cap = g_trace_cap;
-  TORCH_CHECK((cfg >= 0 && cfg < tfsk::kNumIGemmConfigs) || is_cgemm_cfg(cfg) || is_halo_cfg(cfg),
-              "bad tile config ", cfg);
+  TORCH_CHECK(config_of(cfg) != nullptr, "bad tile config ", cfg);
   TORCH_CHECK(!is_cgemm_cfg(cfg) || tfsk::cgemm_supported(a, a_mode),
               "tile config ", cfg, " needs 64-aligned operands (K % 64, C % 64)");
   TORCH_CHECK(!is_halo_cfg(cfg) || (a_mode == tfsk::kAIm2col && tfsk::halo_supported(a)),
@@ -146,7 +143,8 @@ void set_post(tfsk::IGemmArgs& a, const c10::optional<Tensor>& scale, const c10:
   need(*shift, at::kFloat, "post_shift");
   TORCH_CHECK(scale->numel() == cout && shift->numel() == cout, "post scale / shift must have Cout entries");
   TORCH_CHECK(aligned16(*scale) && aligned16(*shift), "post scale / shift must be 16-B aligned");
-  TORCH_CHECK(cfg >= tfsk::kCGemmCfgBase || splits > 1, "the post-activation output needs a cgemm / halo config");
+  TORCH_CHECK(is_cgemm_cfg(cfg) || is_halo_cfg(cfg) || splits > 1,
+              "the post-activation output needs a cgemm / halo config");
   a.scale2 = scale->data_ptr<float>();
   a.shift2 = shift->data_ptr<float>();
   a.act2 = int(act2);
@@ -335,7 +333,7 @@ std::vector<Tensor> linear_lnx(const Tensor& x, const Tensor& w, const c10::opti
   const int N = w.size(0), ldb = w.size(1);
   TORCH_CHECK(ldb >= K && K % 64 == 0 && ldb % 8 == 0 && N % 8 == 0,
               "linear_lnx: K % 64 == 0 (fitting in w), N % 8 == 0");
-  TORCH_CHECK(is_cgemm_cfg(cfg) && !(cfg >= tfsk::kBGemmCfgBase && cfg < tfsk::kBGemmCfgBase + tfsk::kNumBGemmConfigs),
+  TORCH_CHECK(is_cgemm_cfg(cfg) && config_of(cfg)->family != tfsk::TileFamily::kBGemm,
               "linear_lnx: a cgemm tile config");
   TORCH_CHECK(!(stats && out_f32), "linear_lnx: row statistics of bf16 outputs only");
   auto sizes = x.sizes().vec();
@@ -964,23 +962,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     return tfsk::classifier_head_one_launch(int(M), int(HW), int(K), int(Np), int(n));
   });
   m.def("num_configs", []() { return tfsk::kNumIGemmConfigs; });
-  m.def("cgemm_configs", []() {
+  // (in the order of the rows of tile_configs.h; the GPU tests parametrize over them)
+  auto ids_where = [](bool (*in_family)(tfsk::TileFamily)) {
     std::vector<int> v;
-    for (int c = 0; c < tfsk::kNumCGemmConfigs; ++c) v.push_back(tfsk::kCGemmCfgBase + c);
-    for (int c = 0; c < tfsk::kNumCGemmConfigs2; ++c) v.push_back(tfsk::kCGemmCfgBase2 + c);
-    for (int c = 0; c < tfsk::kNumCGemmPfConfigs; ++c) v.push_back(tfsk::kCGemmPfCfgBase + c);
-    for (int c = 0; c < tfsk::kNumCGemm32Configs; ++c) v.push_back(tfsk::kCGemm32CfgBase + c);
-    for (int c = 0; c < tfsk::kNumBGemmConfigs; ++c) v.push_back(tfsk::kBGemmCfgBase + c);
+    for (int i = 0; i < tfsk::kTileTable.n; ++i)
+      if (in_family(tfsk::kTileTable.rows[i].family)) v.push_back(tfsk::kTileTable.rows[i].id);
     return v;
-  });
-  m.def("halo_configs", []() {
-    std::vector<int> v;
-    for (int c = 0; c < tfsk::kNumHaloConfigs; ++c) v.push_back(tfsk::kHaloCfgBase + c);
-    for (int c = 0; c < tfsk::kNumHaloConfigs; ++c)
-      if (tfsk::halo_cfg_id(tfsk::kHaloPfCfgBase + c)) v.push_back(tfsk::kHaloPfCfgBase + c);
-    v.push_back(tfsk::kHaloPersistCfg);
-    return v;
-  });
+  };
+  m.def("cgemm_configs", [ids_where]() { return ids_where(tfsk::cgemm_family); });
+  m.def("halo_configs", [ids_where]() { return ids_where(tfsk::halo_family); });
   m.def("halo_persist_tiles", [](int64_t n, int64_t ho, int64_t wo) {
     long tiles = 0;
     int th = 0, tw = 0, ti = 0;
@@ -990,9 +980,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     return std::make_tuple(int64_t(tiles), th, tw, ti);
   }, py::arg("n"), py::arg("ho"), py::arg("wo"),
      "(tiles, TH, TW, TI) of config 146's launch for n images of ho x wo outputs (host only; launches nothing)");
-  m.def("config_tile", [](int cfg) {
-    if (is_halo_cfg(cfg)) return std::make_pair(tfsk::halo_config_bm(cfg), tfsk::halo_config_bn(cfg));
-    if (is_cgemm_cfg(cfg)) return std::make_pair(tfsk::cgemm_config_bm(cfg), tfsk::cgemm_config_bn(cfg));
-    return std::make_pair(tfsk::igemm_config_bm(cfg), tfsk::igemm_config_bn(cfg));
-  });
+  m.def("config_tile", [](int64_t cfg) {
+    const tfsk::TileConfig* c = config_of(cfg);
+    TORCH_CHECK(c != nullptr, "bad tile config ", cfg);
+    return std::make_pair(c->bm, c->bn);
+  }, "(BM, BN) of a tile config; raises for an id that is not one");
 }

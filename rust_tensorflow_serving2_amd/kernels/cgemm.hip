@@ -39,48 +39,15 @@ namespace {
 using namespace gemm;
 using cgemm_impl::launch_cfg;
 
-// Config table (tile BM x BN, wave grid, ring depth).  LDS per workgroup =
-// S * (BM + BN) * 128 B (or the fp32 epilogue tile if larger).
-constexpr int kAll = kNumCGemmConfigs + kNumCGemmConfigs2;
-constexpr int kBM[kAll] = {128, 128, 64, 128, 64, 256, 128, 128, 64, 256, 64, 64, 128, 128, 128, 64,
-                           64, 64, 64, 128, 64, 128, 64, 64, 256, 256, 128, 128};
-constexpr int kBN[kAll] = {128, 128, 128, 64, 64, 128, 256, 128, 256, 64, 64, 128, 64, 96, 96, 96,
-                           64, 64, 64, 64, 128, 64, 128, 64, 192, 144, 96, 96};
-
-// PF config ids kCGemmPfCfgBase + i: the fragment-prefetch build of table index kPfOf[i]
-// (the 8-wave 256 x 128 / 128 x 256 / 256 x 192 tiles spill with two fragment sets: not built)
-constexpr int kPfOf[kNumCGemmPfConfigs] = {0, 2, 3, 4, 7, 9, 10, 11, 12, 13, 23};
-
-// 32x32x16 MFMA builds (ids kCGemm32CfgBase + i): BM x BN, wave grid, ring depth
-constexpr int k32BM[kNumCGemm32Configs] = {64, 64, 128, 128, 64, 128, 256, 256, 128, 64, 128, 256};
-constexpr int k32BN[kNumCGemm32Configs] = {64, 64, 128, 64, 128, 256, 128, 64, 128, 128, 64, 192};
-
-// big-tile ping-pong builds (ids kBGemmCfgBase + i, bgemm.hip)
-constexpr int kBBM[kNumBGemmConfigs] = {256, 256, 256};
-constexpr int kBBN[kNumBGemmConfigs] = {256, 128, 192};
-
-// config id -> index into the tables (all id ranges; the 32x32 range indexes k32BM / k32BN)
-int cfg_index(int cfg) {
-  if (cfg >= kBGemmCfgBase) return cfg - kBGemmCfgBase;
-  if (cfg >= kCGemm32CfgBase) return cfg - kCGemm32CfgBase;
-  if (cfg >= kCGemmPfCfgBase) return kPfOf[cfg - kCGemmPfCfgBase];
-  return cfg < kCGemmCfgBase2 ? cfg - kCGemmCfgBase : kNumCGemmConfigs + (cfg - kCGemmCfgBase2);
-}
-
+// The configs are the TFSK_CGEMM_CONFIGS / TFSK_CGEMM_PF_CONFIGS rows of
+// tile_configs.h (tile BM x BN, wave grid, ring depth).
 template <int AM>
-hipError_t launch_mode_pf(const IGemmArgs& a, int idx, hipStream_t s) {
-  switch (idx) {
-    case 0: return launch_cfg<128, 128, 2, 2, 3, AM, true>(a, s);
-    case 2: return launch_cfg<64, 128, 2, 2, 4, AM, true>(a, s);
-    case 3: return launch_cfg<128, 64, 2, 2, 4, AM, true>(a, s);
-    case 4: return launch_cfg<64, 64, 2, 2, 4, AM, true>(a, s);
-    case 7: return launch_cfg<128, 128, 2, 4, 4, AM, true>(a, s);
-    case 9: return launch_cfg<256, 64, 4, 1, 3, AM, true>(a, s);
-    case 10: return launch_cfg<64, 64, 2, 2, 2, AM, true>(a, s);
-    case 11: return launch_cfg<64, 128, 2, 2, 2, AM, true>(a, s);
-    case 12: return launch_cfg<128, 64, 2, 2, 2, AM, true>(a, s);
-    case 13: return launch_cfg<128, 96, 2, 2, 3, AM, true>(a, s);
-    case 23: return launch_cfg<64, 64, 2, 2, 3, AM, true>(a, s);
+hipError_t launch_mode_pf(const IGemmArgs& a, int cfg, hipStream_t s) {
+  switch (cfg) {
+#define TFSK_CASE(id, base, BM, BN, WGM, WGN, S) \
+  case id: return launch_cfg<BM, BN, WGM, WGN, S, AM, true>(a, s);
+    TFSK_CGEMM_PF_CONFIGS(TFSK_CASE)
+#undef TFSK_CASE
     default: return hipErrorInvalidValue;
   }
 }
@@ -88,67 +55,23 @@ hipError_t launch_mode_pf(const IGemmArgs& a, int idx, hipStream_t s) {
 template <int AM>
 hipError_t launch_mode(const IGemmArgs& a, int cfg, hipStream_t s) {
   switch (cfg) {
-    case 0: return launch_cfg<128, 128, 2, 2, 3, AM>(a, s);   // 96 KB, wave 64x64
-    case 1: return launch_cfg<128, 128, 2, 2, 2, AM>(a, s);   // 64 KB (2 WG/CU)
-    case 2: return launch_cfg<64, 128, 2, 2, 4, AM>(a, s);    // 96 KB, wave 32x64
-    case 3: return launch_cfg<128, 64, 2, 2, 4, AM>(a, s);    // 96 KB, wave 64x32
-    case 4: return launch_cfg<64, 64, 2, 2, 4, AM>(a, s);     // 64 KB, wave 32x32
-    case 5: return launch_cfg<256, 128, 4, 2, 3, AM>(a, s);   // 144 KB, 8 waves of 64x64
-    case 6: return launch_cfg<128, 256, 2, 4, 3, AM>(a, s);   // 144 KB, 8 waves of 64x64
-    case 7: return launch_cfg<128, 128, 2, 4, 4, AM>(a, s);   // 128 KB, 8 waves of 64x32
-    case 8: return launch_cfg<64, 256, 1, 4, 3, AM>(a, s);    // 120 KB, wave 64x64
-    case 9: return launch_cfg<256, 64, 4, 1, 3, AM>(a, s);    // 120 KB, wave 64x64
-    // double-buffered, small LDS: several workgroups per CU overlap each
-    // other's prologue / barrier / epilogue latency
-    case 10: return launch_cfg<64, 64, 2, 2, 2, AM>(a, s);    // 32 KB (5 WG/CU)
-    case 11: return launch_cfg<64, 128, 2, 2, 2, AM>(a, s);   // 48 KB (3 WG/CU)
-    case 12: return launch_cfg<128, 64, 2, 2, 2, AM>(a, s);   // 48 KB (3 WG/CU)
-    // 96-wide tiles: N = 768 (BERT-base hidden) is 8 of them, so an M = 4096
-    // GEMM is exactly 256 tiles of 128 x 96 -- one per CU -- where 128 x 128
-    // leaves a quarter of the CUs idle (192 tiles) and 128 x 64 needs 1.5 waves
-    case 13: return launch_cfg<128, 96, 2, 2, 3, AM>(a, s);   // 84 KB, wave 64x48
-    case 14: return launch_cfg<128, 96, 2, 2, 4, AM>(a, s);   // 112 KB
-    case 15: return launch_cfg<64, 96, 2, 2, 3, AM>(a, s);    // 60 KB, wave 32x48
-    // two waves per workgroup: a 64x64 tile as two 64x32 wave tiles reads 24 KB
-    // of LDS fragments per k-step instead of the 32 KB four 32x32 waves read
-    // (whose LDS reads take as long as their MFMAs at 256 B/clk)
-    case 16: return launch_cfg<64, 64, 1, 2, 2, AM>(a, s);    // 32 KB, wave 64x32
-    case 17: return launch_cfg<64, 64, 1, 2, 3, AM>(a, s);    // 48 KB
-    case 18: return launch_cfg<64, 64, 2, 1, 3, AM>(a, s);    // 48 KB, wave 32x64
-    case 19: return launch_cfg<128, 64, 2, 1, 2, AM>(a, s);   // 48 KB, wave 64x64
-    case 20: return launch_cfg<64, 128, 1, 2, 2, AM>(a, s);   // 48 KB, wave 64x64
-    case 21: return launch_cfg<128, 64, 2, 1, 3, AM>(a, s);   // 72 KB, wave 64x64
-    case 22: return launch_cfg<64, 128, 1, 2, 3, AM>(a, s);   // 72 KB, wave 64x64
-    case 23: return launch_cfg<64, 64, 2, 2, 3, AM>(a, s);    // 48 KB, wave 32x32
-    // 8 waves of 64x96 (BERT's 2304 / 3072-wide projections at M = 4096: 192 /
-    // 256 tiles, one per CU); 112 KB ring, epilogue in two 128-row passes
-    case 24: return launch_cfg<256, 192, 4, 2, 2, AM>(a, s);
-    // 8 waves of 32x144: BERT-base's QKV projection (4096 x 2304) is exactly
-    // 256 tiles of 256 x 144, one per CU, where 256 x 192 leaves 64 CUs idle
-    // (192 tiles); 150 KB, a 3-slot ring, the fp32 epilogue in one pass
-    case 25: return launch_cfg<256, 144, 8, 1, 3, AM>(a, s);
-    // 8 waves of 32x48 on the 128 x 96 tile (N = 768 at M = 4096: 256 tiles):
-    // two waves per SIMD to cover the DMA latency the 4-wave 128 x 96 builds
-    // (ids 45 / 46) leave exposed over K = 3072; 4- and 5-slot rings
-    case 26: return launch_cfg<128, 96, 4, 2, 4, AM>(a, s);   // 112 KB
-    case 27: return launch_cfg<128, 96, 4, 2, 5, AM>(a, s);   // 140 KB
+#define TFSK_CASE(id, BM, BN, WGM, WGN, S) \
+  case id: return launch_cfg<BM, BN, WGM, WGN, S, AM>(a, s);
+    TFSK_CGEMM_CONFIGS(TFSK_CASE)
+#undef TFSK_CASE
     default: return hipErrorInvalidValue;
   }
 }
 
 }  // namespace
 
-int cgemm_config_bm(int cfg) {
-  return cfg >= kBGemmCfgBase ? kBBM[cfg_index(cfg)]
-         : cfg >= kCGemm32CfgBase ? k32BM[cfg_index(cfg)] : kBM[cfg_index(cfg)];
-}
-int cgemm_config_bn(int cfg) {
-  return cfg >= kBGemmCfgBase ? kBBN[cfg_index(cfg)]
-         : cfg >= kCGemm32CfgBase ? k32BN[cfg_index(cfg)] : kBN[cfg_index(cfg)];
-}
+// (0 / false for an id that is not a cgemm config)
+int cgemm_config_bm(int cfg) { return cgemm_cfg_id(cfg) ? tile_config(cfg)->bm : 0; }
+int cgemm_config_bn(int cfg) { return cgemm_cfg_id(cfg) ? tile_config(cfg)->bn : 0; }
 
 bool cgemm_fixup_ok(int cfg) {
-  if (cfg >= kBGemmCfgBase) return false;            // no in-kernel fixup (bgemm)
+  // bgemm has no in-kernel fixup
+  if (!cgemm_cfg_id(cfg) || tile_config(cfg)->family == TileFamily::kBGemm) return false;
   // the in-kernel split-K fixup needs the whole fp32 tile in LDS at once (one pass)
   return size_t(cgemm_config_bm(cfg)) * (cgemm_config_bn(cfg) + 4) * 4 <= 160 * 1024;
 }
@@ -173,18 +96,17 @@ bool cgemm_supported(const IGemmArgs& a, int a_mode) {
 
 hipError_t cgemm_launch(const IGemmArgs& a, int a_mode, int cfg, hipStream_t s) {
   if (!cgemm_cfg_id(cfg) || !cgemm_supported(a, a_mode)) return hipErrorInvalidValue;
-  if (cfg >= kBGemmCfgBase) return bgemm_launch(a, a_mode, cfg_index(cfg), s);
-  if (cfg >= kCGemm32CfgBase) return cgemm32_launch(a, a_mode, cfg_index(cfg), s);
-  if (cfg >= kCGemmPfCfgBase) {
-    const int idx = cfg_index(cfg);
+  const TileFamily family = tile_config(cfg)->family;
+  if (family == TileFamily::kBGemm) return bgemm_launch(a, a_mode, cfg, s);
+  if (family == TileFamily::kCGemm32) return cgemm32_launch(a, a_mode, cfg, s);
+  if (family == TileFamily::kCGemmPf) {
     switch (a_mode) {
-      case kAIm2col: return launch_mode_pf<1>(a, idx, s);
-      case kADual: return launch_mode_pf<2>(a, idx, s);
-      case kAC4: return launch_mode_pf<3>(a, idx, s);
-      default: return launch_mode_pf<0>(a, idx, s);
+      case kAIm2col: return launch_mode_pf<1>(a, cfg, s);
+      case kADual: return launch_mode_pf<2>(a, cfg, s);
+      case kAC4: return launch_mode_pf<3>(a, cfg, s);
+      default: return launch_mode_pf<0>(a, cfg, s);
     }
   }
-  cfg = cfg_index(cfg);
   switch (a_mode) {
     case kAIm2col: return launch_mode<1>(a, cfg, s);
     case kADual: return launch_mode<2>(a, cfg, s);

@@ -443,7 +443,7 @@ __global__ __launch_bounds__(64 * WGM * WGN) void halo_conv_kernel(IGemmArgs p) 
 }
 
 // ---------------------------------------------------------------- persistent halo conv
-// halo_persist_kernel (id kHaloPersistCfg): the 3x3 layers whose whole filter
+// halo_persist_kernel (the TFSK_HALO_PERSIST_CONFIGS row): the 3x3 layers whose whole filter
 // fits in LDS -- one 64-channel input chunk and 64 output channels (ResNet-50
 // stage 1, 56x56x64 -> 64: 9 taps x 64 x 64 bf16 = 72 KB).  halo_conv_kernel
 // runs them as ~1.75 waves of workgroups that all wait for their first halo at
@@ -468,7 +468,9 @@ __global__ __launch_bounds__(64 * WGM * WGN) void halo_conv_kernel(IGemmArgs p) 
 // its opening wait, 5 tile 1 after its K loop, 6 exit (stores drained).  They
 // are compiled into the TRACE instance only, which the launcher picks when a
 // trace buffer is set: the production instance carries none of their branches.
-constexpr int kPersistBM = 128, kPersistBN = 64, kPersistHR = 192;
+#define TFSK_PERSIST(id, BM, BN, HR) constexpr int kPersistBM = BM, kPersistBN = BN, kPersistHR = HR;
+TFSK_HALO_PERSIST_CONFIGS(TFSK_PERSIST)
+#undef TFSK_PERSIST
 struct HPs {
   static constexpr int BM = kPersistBM, BN = kPersistBN, HR = kPersistHR;
   static constexpr int WGM = 4, WGN = 2, NW = 8, NT = 512;
@@ -795,15 +797,21 @@ hipError_t launch_halo_persist(const IGemmArgs& a0, hipStream_t s) {
   return hipGetLastError();
 }
 
-// per config index (halo_cfg_index)
-constexpr int kHBM[kNumHaloConfigs] = {256, 128, 128, 64, 256, 64, 64, 128, 256, 128, 128};
-constexpr int kHBN[kNumHaloConfigs] = {64, 128, 64, 64, 128, 128, 64, 64, 64, 64, 64};
-constexpr int kHHR[kNumHaloConfigs] = {320, 192, 192, 128, 320, 128, 128, 192, 320, 192, 192};     // halo rows (HR)
-
-int halo_cfg_index(int cfg) {
-  if (cfg >= kHaloCfgBase && cfg < kHaloCfgBase + kNumHaloConfigs) return cfg - kHaloCfgBase;
-  if (cfg >= kHaloPfCfgBase && cfg < kHaloPfCfgBase + kNumHaloConfigs) return cfg - kHaloPfCfgBase;
-  return -1;
+// The TFSK_HALO_CONFIGS rows: the plain builds under their ids, the
+// fragment-prefetch builds (PF) under the rows' pf_id where there is one.
+template <bool PF>
+hipError_t launch_halo_row(const IGemmArgs& a, int cfg, hipStream_t s) {
+  switch (cfg) {
+#define TFSK_CASE(id, pf_id, BM, BN, WGM, WGN, HR, S)             \
+  case (PF ? (pf_id != 0 ? pf_id : -id) : id):                    \
+    if constexpr (!PF || pf_id != 0)                              \
+      return launch_halo_cfg<BM, BN, WGM, WGN, HR, S, PF>(a, s);  \
+    break;
+    TFSK_HALO_CONFIGS(TFSK_CASE)
+#undef TFSK_CASE
+    default: break;
+  }
+  return hipErrorInvalidValue;
 }
 
 }  // namespace
@@ -811,14 +819,14 @@ int halo_cfg_index(int cfg) {
 long halo_tiles(const IGemmArgs& a0, int cfg) {
   IGemmArgs a = a0;
   a.epi_f32 = epi_f32_env();
-  if (cfg == kHaloPersistCfg) return 0;   // no split-K (no fixup counters)
-  const int c = halo_cfg_index(cfg);
-  if (c < 0) return 0;
-  if (!pick_block(a.Ho, a.Wo, kHBM[c], kHHR[c], a.TH, a.TW)) return 0;
+  const TileConfig* c = tile_config(cfg);
+  // (the persistent kernel: no split-K, no fixup counters)
+  if (c == nullptr || (c->family != TileFamily::kHalo && c->family != TileFamily::kHaloPf)) return 0;
+  if (!pick_block(a.Ho, a.Wo, c->bm, c->hr, a.TH, a.TW)) return 0;
   const int nimg = a.M / (a.Ho * a.Wo);
-  const int ti = pick_images(a, kHBM[c], kHHR[c]);
+  const int ti = pick_images(a, c->bm, c->hr);
   return long((nimg + ti - 1) / ti) * ((a.Ho + a.TH - 1) / a.TH) * ((a.Wo + a.TW - 1) / a.TW) *
-         ((a.N + kHBN[c] - 1) / kHBN[c]);
+         ((a.N + c->bn - 1) / c->bn);
 }
 
 bool halo_persist_tiles(int n, int ho, int wo, long& tiles, int& th, int& tw, int& ti) {
@@ -841,46 +849,16 @@ bool halo_supported(const IGemmArgs& a) {
          a.M < (1 << 23) && int64_t(a.M / (a.Ho * a.Wo)) * a.H * a.W * a.C < (1LL << 30);
 }
 
-int halo_config_bm(int cfg) { return cfg == kHaloPersistCfg ? kPersistBM : kHBM[halo_cfg_index(cfg)]; }
-int halo_config_bn(int cfg) { return cfg == kHaloPersistCfg ? kPersistBN : kHBN[halo_cfg_index(cfg)]; }
+// (0 for an id that is not a halo config)
+int halo_config_bm(int cfg) { return halo_cfg_id(cfg) ? tile_config(cfg)->bm : 0; }
+int halo_config_bn(int cfg) { return halo_cfg_id(cfg) ? tile_config(cfg)->bn : 0; }
 
 hipError_t halo_launch(const IGemmArgs& a, int cfg, hipStream_t s) {
   if (!halo_cfg_id(cfg) || !halo_supported(a)) return hipErrorInvalidValue;
-  if (cfg == kHaloPersistCfg) return launch_halo_persist(a, s);
-  if (cfg >= kHaloPfCfgBase) {
-    switch (halo_cfg_index(cfg)) {   // the same tiles with the fragment-prefetch step pipeline
-      case 0: return launch_halo_cfg<256, 64, 4, 1, 320, 3, true>(a, s);
-      case 1: return launch_halo_cfg<128, 128, 2, 2, 192, 3, true>(a, s);
-      case 2: return launch_halo_cfg<128, 64, 2, 2, 192, 3, true>(a, s);
-      case 3: return launch_halo_cfg<64, 64, 2, 2, 128, 3, true>(a, s);
-      // (4: the 8-wave 256 x 128 tile spills with two fragment sets; not built)
-      case 5: return launch_halo_cfg<64, 128, 2, 2, 128, 3, true>(a, s);
-      case 6: return launch_halo_cfg<64, 64, 2, 2, 128, 9, true>(a, s);
-      case 7: return launch_halo_cfg<128, 64, 2, 2, 192, 9, true>(a, s);
-      case 8: return launch_halo_cfg<256, 64, 4, 1, 320, 9, true>(a, s);
-      case 9: return launch_halo_cfg<128, 64, 4, 2, 192, 3, true>(a, s);
-      case 10: return launch_halo_cfg<128, 64, 4, 2, 192, 9, true>(a, s);
-      default: return hipErrorInvalidValue;
-    }
-  }
-  switch (halo_cfg_index(cfg)) {
-    // LDS = 2 halo buffers (HR x 128 B; one when C == 64) + S B slots (BN x 128 B)
-    case 0: return launch_halo_cfg<256, 64, 4, 1, 320, 3>(a, s);    // 104 KB (64 KB for C == 64), waves 64x64
-    case 1: return launch_halo_cfg<128, 128, 2, 2, 192, 3>(a, s);   // 96 KB, waves 64x64
-    case 2: return launch_halo_cfg<128, 64, 2, 2, 192, 3>(a, s);    // 72 KB (48 KB), waves 64x32
-    case 3: return launch_halo_cfg<64, 64, 2, 2, 128, 3>(a, s);     // 56 KB (40 KB), waves 32x32
-    case 4: return launch_halo_cfg<256, 128, 4, 2, 320, 3>(a, s);   // 135 KB, 8 waves of 64x64
-    case 5: return launch_halo_cfg<64, 128, 2, 2, 128, 3>(a, s);    // 80 KB, waves 32x64
-    // 9-slot rings: 8 weight tiles in flight (16 x 1-KB DMAs per wave)
-    case 6: return launch_halo_cfg<64, 64, 2, 2, 128, 9>(a, s);     // 104 KB, waves 32x32
-    case 7: return launch_halo_cfg<128, 64, 2, 2, 192, 9>(a, s);    // 120 KB, waves 64x32
-    case 8: return launch_halo_cfg<256, 64, 4, 1, 320, 9>(a, s);    // 152 KB, waves 64x64
-    // 8 waves of 32x32 on the 128 x 64 tile: two waves per SIMD where the
-    // 4-wave build waits 40 % of its cycles (the stage-2 / 3 3x3 convs,
-    // profiles/round4/s5/pmc_r50_b32_mfma.txt)
-    case 9: return launch_halo_cfg<128, 64, 4, 2, 192, 3>(a, s);    // 72 KB
-    case 10: return launch_halo_cfg<128, 64, 4, 2, 192, 9>(a, s);   // 120 KB
-    default: return hipErrorInvalidValue;
+  switch (tile_config(cfg)->family) {
+    case TileFamily::kHaloPersist: return launch_halo_persist(a, s);
+    case TileFamily::kHaloPf: return launch_halo_row<true>(a, cfg, s);
+    default: return launch_halo_row<false>(a, cfg, s);
   }
 }
 

@@ -635,58 +635,28 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(IGemmArgs p) {
   }
 }
 
-// Tile configs: (BM, BN, DMA ring depth).  Deeper rings hide more memory
-// latency per workgroup but cost LDS, i.e. resident workgroups per CU (160 KB
-// LDS): the tuner picks per layer (K=64 1x1 convs want occupancy, long-K
-// small-grid layers want depth).  Register-staged operand modes ignore the
-// depth (always 2).
-constexpr int kCfgBM[kNumIGemmConfigs] = {128, 128, 64, 64, 128, 64, 128, 64, 64, 256, 128, 256, 64, 64, 64, 128, 128};
-constexpr int kCfgBN[kNumIGemmConfigs] = {128, 64, 128, 64, 128, 64, 64, 128, 256, 64, 256, 128, 64, 64, 128, 64, 128};
-constexpr int kCfgST[kNumIGemmConfigs] = {2, 2, 2, 2, 3, 4, 3, 3, 2, 2, 2, 2, 2, 2, 2, 2, 2};
-constexpr int kCfgBK[kNumIGemmConfigs] = {64, 64, 64, 64, 64, 64, 64, 64, 64, 64, 64, 64, 128, 256, 128, 128, 128};
-// register-staged operand modes only instantiate configs 0-3
-constexpr int kCfgBase[kNumIGemmConfigs] = {0, 1, 2, 3, 0, 3, 1, 2, 2, 1, 0, 0, 3, 3, 2, 1, 0};
-
+// The TFSK_IGEMM_CONFIGS rows of tile_configs.h.  The direct-to-LDS operand
+// modes (GL) build every row; the register-staged ones build the rows that are
+// their own base and run every other id as its base.
 template <int AMODE>
 hipError_t launch_mode(const IGemmArgs& a, int cfg, hipStream_t s) {
   constexpr bool GL = (AMODE == kADense || AMODE == kAIm2col);
-  if (!GL) cfg = kCfgBase[cfg];
-  switch (cfg) {
-    case 0: return launch_cfg<128, 128, AMODE, 2>(a, s);
-    case 1: return launch_cfg<128, 64, AMODE, 2>(a, s);
-    case 2: return launch_cfg<64, 128, AMODE, 2>(a, s);
-    case 3: return launch_cfg<64, 64, AMODE, 2>(a, s);
+  const TileConfig* c = tile_config(cfg);
+  if (c == nullptr || c->family != TileFamily::kIGemm) return hipErrorInvalidValue;
+  switch (GL ? cfg : c->base) {
+#define TFSK_CASE(id, BM, BN, ST, WAVES_M, BK, base)             \
+  case id:                                                       \
+    if constexpr (GL || id == base)                              \
+      return launch_cfg<BM, BN, AMODE, ST, WAVES_M, BK>(a, s);   \
+    break;
+    TFSK_IGEMM_CONFIGS(TFSK_CASE)
+#undef TFSK_CASE
     default: break;
-  }
-  if constexpr (GL) {
-    switch (cfg) {
-      case 4: return launch_cfg<128, 128, AMODE, 3>(a, s);
-      case 5: return launch_cfg<64, 64, AMODE, 4>(a, s);
-      case 6: return launch_cfg<128, 64, AMODE, 3>(a, s);
-      case 7: return launch_cfg<64, 128, AMODE, 3>(a, s);
-      // wide tiles (one wave row / column): 4x the outputs per workgroup setup
-      case 8: return launch_cfg<64, 256, AMODE, 2, 1>(a, s);
-      case 9: return launch_cfg<256, 64, AMODE, 2, 4>(a, s);
-      case 10: return launch_cfg<128, 256, AMODE, 2, 2>(a, s);
-      case 11: return launch_cfg<256, 128, AMODE, 2, 4>(a, s);
-      // deep k-tiles: 2-4x the MFMA work per barrier / DMA round trip
-      case 12: return launch_cfg<64, 64, AMODE, 2, 2, 128>(a, s);
-      case 13: return launch_cfg<64, 64, AMODE, 2, 2, 256>(a, s);
-      case 14: return launch_cfg<64, 128, AMODE, 2, 2, 128>(a, s);
-      case 15: return launch_cfg<128, 64, AMODE, 2, 2, 128>(a, s);
-      case 16: return launch_cfg<128, 128, AMODE, 2, 2, 128>(a, s);
-      default: break;
-    }
   }
   return hipErrorInvalidValue;
 }
 
 }  // namespace
-
-int igemm_config_bm(int cfg) { return kCfgBM[cfg]; }
-int igemm_config_bn(int cfg) { return kCfgBN[cfg]; }
-int igemm_config_stages(int cfg) { return kCfgST[cfg]; }
-int igemm_config_bk(int cfg) { return kCfgBK[cfg]; }
 
 hipError_t igemm_launch(const IGemmArgs& a, int a_mode, int cfg, hipStream_t s) {
   switch (a_mode) {

@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "tile_configs.h"
+
 namespace tfsk {
 
 // Implicit-GEMM geometry.  GEMM view: C[M][N] = A[M][K] * B[N][K]^T where
@@ -133,15 +135,8 @@ hipError_t ingest_c4_pad_launch(const float* x, uint16_t* y, int N, int H, int W
 // Sum split-K partial slabs and apply the epilogue (bias, residual, act, store).
 hipError_t splitk_reduce_launch(const IGemmArgs& args, hipStream_t stream);
 
-// Tile configs (BM x BN, DMA ring depth): 0..3 = 128x128, 128x64, 64x128,
-// 64x64 double-buffered; 4 = 128x128x3, 5 = 64x64x4, 6 = 128x64x3, 7 = 64x128x3;
-// wide: 8 = 64x256, 9 = 256x64, 10 = 128x256, 11 = 256x128 (dense / im2col only)
-// deep k-tiles (BK): 12 = 64x64/128, 13 = 64x64/256, 14 = 64x128/128, 15 = 128x64/128, 16 = 128x128/128
-constexpr int kNumIGemmConfigs = 17;
-int igemm_config_bm(int cfg);
-int igemm_config_bn(int cfg);
-int igemm_config_stages(int cfg);
-int igemm_config_bk(int cfg);
+// Tile configs 0 .. kNumIGemmConfigs - 1: the TFSK_IGEMM_CONFIGS rows of
+// tile_configs.h; any other cfg is hipErrorInvalidValue.
 hipError_t igemm_launch(const IGemmArgs& args, int a_mode, int cfg, hipStream_t stream);
 
 // Fused ResNet stem (stem.hip): fp32 [N][H][W][C<=4] -> 7x7/2 conv (weights

@@ -17,6 +17,8 @@ from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
 import torch
 
+from . import tile_table
+
 _HIP = None
 _LOCK = threading.Lock()
 
@@ -138,44 +140,42 @@ def heuristic_config(M: int, N: int) -> int:
     return 3
 
 
-# (BM, BN) per igemm config; configs 4.. add deeper direct-to-LDS DMA rings
-# (kernels/igemm.hip kCfgST) and only apply to dense / im2col operands.
-TILES = {0: (128, 128), 1: (128, 64), 2: (64, 128), 3: (64, 64),
-         4: (128, 128), 5: (64, 64), 6: (128, 64), 7: (64, 128),
-         8: (64, 256), 9: (256, 64), 10: (128, 256), 11: (256, 128),
-         12: (64, 64), 13: (64, 64), 14: (64, 128), 15: (128, 64), 16: (128, 128)}
-DMA_ONLY = {4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16}
-TILE_BK = {12: 128, 13: 256, 14: 128, 15: 128, 16: 128}     # k-tile depth (default 64)
-# pipelined cgemm kernel (kernels/cgemm.hip; 64-aligned operands only): config id -> (BM, BN)
-CGEMM = {32: (128, 128), 33: (128, 128), 34: (64, 128), 35: (128, 64), 36: (64, 64),
-         37: (256, 128), 38: (128, 256), 39: (128, 128), 40: (64, 256), 41: (256, 64),
-         42: (64, 64), 43: (64, 128), 44: (128, 64), 45: (128, 96), 46: (128, 96), 47: (64, 96),
-         64: (64, 64), 65: (64, 64), 66: (64, 64), 67: (128, 64), 68: (64, 128), 69: (128, 64), 70: (64, 128),
-         71: (64, 64), 72: (256, 192), 73: (256, 144), 74: (128, 96), 75: (128, 96)}
-# fragment-prefetch (PF) builds of 11 of those tiles (kernels/cgemm.hip kPfOf)
-CGEMM_PF_OF = [32, 34, 35, 36, 39, 41, 42, 43, 44, 45, 71]
-CGEMM.update({96 + k: CGEMM[base] for k, base in enumerate(CGEMM_PF_OF)})
-# v_mfma_f32_32x32x16_bf16 builds (kernels/cgemm32.hip, ids 112..123: wave tiles in 32x32 blocks)
-CGEMM32 = {112: (64, 64), 113: (64, 64), 114: (128, 128), 115: (128, 64), 116: (64, 128), 117: (128, 256),
-           118: (256, 128), 119: (256, 64), 120: (128, 128), 121: (64, 128), 122: (128, 64), 123: (256, 192)}
+# The tile configs, config id -> (BM, BN), read from kernels/tile_configs.h (the
+# rows the launchers are built from; the per-config notes are on the rows).
+# The insertion order of these dicts is the order candidates() lists configs
+# in, which decides ties in the tuner.
+_ROWS = tile_table.read_rows()
+# igemm: the rows that are not their own `base` add deeper direct-to-LDS DMA
+# rings / wide tiles / deep k-tiles and only apply to dense / im2col operands
+TILES = {r[0]: (r[1], r[2]) for r in _ROWS["IGEMM"]}
+DMA_ONLY = {r[0] for r in _ROWS["IGEMM"] if r[6] != r[0]}
+TILE_BK = {r[0]: r[5] for r in _ROWS["IGEMM"] if r[5] != 64}     # k-tile depth (default 64)
+# pipelined cgemm kernel (64-aligned operands only)
+CGEMM = {r[0]: (r[1], r[2]) for r in _ROWS["CGEMM"]}
+# fragment-prefetch (PF) builds of some of those tiles: the ids they are builds of
+CGEMM_PF_OF = [r[1] for r in _ROWS["CGEMM_PF"]]
+CGEMM.update({r[0]: (r[2], r[3]) for r in _ROWS["CGEMM_PF"]})
+# v_mfma_f32_32x32x16_bf16 builds (wave tiles in 32x32 blocks)
+CGEMM32 = {r[0]: (r[1], r[2]) for r in _ROWS["CGEMM32"]}
 CGEMM.update(CGEMM32)
-# (ids 124..137, the 32-deep k-tile and persistent multi-tile builds, were removed in round 6:
-# 0 of 192 picks in the round-5 table)
-# big-tile ping-pong builds (kernels/bgemm.hip, ids 140..142): 8 waves of 128 x 64 / 128 x 32 / 128 x 48,
-# dense operands only (other operand modes are rejected at launch and skipped by the tuner)
-BGEMM = {140: (256, 256), 141: (256, 128), 142: (256, 192)}
+# big-tile ping-pong builds: dense operands only (other operand modes are
+# rejected at launch and skipped by the tuner)
+BGEMM = {r[0]: (r[1], r[2]) for r in _ROWS["BGEMM"]}
 CGEMM.update(BGEMM)
 TILES.update(CGEMM)
-# halo-tiled 3x3 stride-1 conv (kernels/halo.hip): config id -> (output pixels per tile, BN)
-HALO = {48: (256, 64), 49: (128, 128), 50: (128, 64), 51: (64, 64), 52: (256, 128), 53: (64, 128), 54: (64, 64),
-        55: (128, 64), 56: (256, 64), 57: (128, 64), 58: (128, 64)}
-# the same tiles with the fragment-prefetch step pipeline (halo.hip PF)
-HALO.update({cfg + 32: tile for cfg, tile in list(HALO.items()) if cfg != 52})
-# (ids 144/145, the ping-pong halo kernel, were removed in round 6: 0 picks)
-# the persistent halo kernel (halo.hip halo_persist_kernel): C == 64 and N == 64, the whole
-# filter resident in LDS, plain bf16 output; other operand modes are rejected at launch
-HALO_PERSIST = 146
-HALO[HALO_PERSIST] = (128, 64)
+# halo-tiled 3x3 stride-1 conv: config id -> (output pixels per tile, BN)
+HALO = {r[0]: (r[2], r[3]) for r in _ROWS["HALO"]}
+# the same tiles with the fragment-prefetch step pipeline, where that build exists
+HALO.update({r[1]: (r[2], r[3]) for r in _ROWS["HALO"] if r[1]})
+# the persistent halo kernel: C == 64 and N == 64, the whole filter resident in
+# LDS, plain bf16 output; other operand modes are rejected at launch
+(_persist,) = _ROWS["HALO_PERSIST"]
+HALO_PERSIST = _persist[0]
+HALO[HALO_PERSIST] = (_persist[1], _persist[2])
+# the configs tuned_config falls back to for a cgemm-only launch it may not
+# time (during graph capture or with autotuning off): the two 64 x 64 tiles,
+# the 4-deep ring where split-K is ruled out, else the double-buffered one
+UNTUNED_CGEMM_NO_SPLIT, UNTUNED_CGEMM = 36, 42
 # TFSERVE_PINGPONG=0: leave the ping-pong builds (bgemm 140-142) out of the
 # tuner's candidates (A/B of the tile tables with and without them)
 PINGPONG = os.environ.get("TFSERVE_PINGPONG", "1") != "0"
@@ -371,7 +371,7 @@ def tuned_config(key: Tuple, M: int, N: int, launch: Callable[[int, int], None],
             _GRAPH_TUNED.add(key)          # the leader already graph-tuned it
         return remote
     if not AUTOTUNE or torch.cuda.is_current_stream_capturing():
-        c = (36 if no_split else 42) if cgemm_only else heuristic_config(M, N)
+        c = (UNTUNED_CGEMM_NO_SPLIT if no_split else UNTUNED_CGEMM) if cgemm_only else heuristic_config(M, N)
         return c, 1 if no_split else heuristic_splits(M, N, K, c)
     with _TUNE_LOCK:
         hit = _TUNED.get(key)

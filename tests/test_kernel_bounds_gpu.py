@@ -23,7 +23,7 @@ if not torch.cuda.is_available():
 
 import kernel_bounds as kb  # noqa: E402
 from kernel_bounds import BF, rnd  # noqa: E402
-from rust_tensorflow_serving2_amd.ops import ACT, hip  # noqa: E402
+from rust_tensorflow_serving2_amd.ops import ACT, BGEMM, HALO_PERSIST, hip  # noqa: E402
 
 DEV = torch.device("cuda:0")
 ACTS = ["none", "relu", "gelu_tanh", "gelu_erf", "tanh"]
@@ -41,15 +41,15 @@ def dev(t):
 
 
 IGEMM_CFGS = list(range(hip().num_configs()))
-BGEMM_CFGS = [140, 141, 142]
+BGEMM_CFGS = list(BGEMM)
 CGEMM_CFGS = [c for c in hip().cgemm_configs() if c not in BGEMM_CFGS]
-HALO_CFGS = [c for c in hip().halo_configs() if c != 146]
+HALO_CFGS = [c for c in hip().halo_configs() if c != HALO_PERSIST]
 
 
 def family_of(cfg):
     if cfg in BGEMM_CFGS:
         return "bgemm"
-    if cfg == 146:
+    if cfg == HALO_PERSIST:
         return "halo_persist"
     if cfg in HALO_CFGS:
         return "halo"
@@ -153,7 +153,7 @@ def test_conv_halo_within_bound(cfg):
 def test_conv_halo_persist_within_bound():
     """Config 146: 64 -> 64 channels, no residual, no split-K."""
     cases = [(5, 7, 9, 64, 64, 3, 1, p) for p in ((1, 1, 1, 1), (0, 2, 1, 0))]
-    run_conv_cases(146, cases, splits_list=(1,), residual=(False,))
+    run_conv_cases(HALO_PERSIST, cases, splits_list=(1,), residual=(False,))
 
 
 @pytest.mark.parametrize("cfg", CGEMM_CFGS + HALO_CFGS)

@@ -22,9 +22,9 @@ Shapes
   M = 6072 (95 / 48 / 24 tiles).  The halo family splits 64-channel chunks, so
   its split-K case has 128 input channels.
 * linear: M = 6341 (a 5-row tail), N = 200, K = 2880.  The deepest LDS ring of
-  any GEMM config is 5 slots (cgemm.hip launch_mode case 27, config id 75:
-  launch_cfg<128, 96, 4, 2, 5>; igemm.hip kCfgST peaks at 4, bgemm.hip
-  ping-pongs two), and the deepest k-tile is 256 (igemm.hip kCfgBK, config 13).
+  any GEMM config is 5 slots (kernels/tile_configs.h: cgemm config id 75,
+  launch_cfg<128, 96, 4, 2, 5>; the igemm stages peak at 4, bgemm.hip
+  ping-pongs two), and the deepest k-tile is 256 (igemm config 13).
   2880 = 45 k-tiles of 64 = 22.5 of 128 = 11.25 of 256: more than 2 * 5
   k-tiles for every config, with a partial k-tile for the deep ones.
 * conv2d_dual / conv_chain: M = 13 * 22 * 22 = 6292 (98.3 tiles of 64) and
