@@ -1,5 +1,6 @@
-// Device helpers shared by the pipelined MFMA GEMM kernels (cgemm.hip,
-// halo.hip) and the host-side per-device LDS attribute cache.
+// Device helpers shared by the MFMA GEMM / conv kernels and the host-side
+// per-device LDS attribute cache.  The epilogue pieces that igemm, bgemm and
+// halo build on them are in gemm_epilogue.h.
 #pragma once
 #include <mutex>
 #include <set>
@@ -41,9 +42,11 @@ __device__ __forceinline__ int fdiv(int a, int d, float inv) {
   return q;
 }
 
-// s_waitcnt vmcnt(N) only (expcnt / lgkmcnt at their maxima; gfx9 encoding).
+// s_waitcnt vmcnt(N) only (expcnt / lgkmcnt at their maxima; gfx9 encoding:
+// vmcnt[3:0] + vmcnt[5:4] at bits 15:14, expcnt 6:4, lgkmcnt 11:8).
 template <int N>
 __device__ __forceinline__ void wait_vmcnt() {
+  static_assert(N >= 0 && N < 64, "vmcnt range");
   __builtin_amdgcn_s_waitcnt((N & 15) | ((N >> 4) << 14) | (7 << 4) | (15 << 8));
 }
 

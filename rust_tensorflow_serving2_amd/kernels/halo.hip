@@ -42,7 +42,7 @@
 #include <algorithm>
 #include <type_traits>
 
-#include "gemm_common.h"
+#include "gemm_epilogue.h"
 #include "cgemm.h"
 
 namespace tfsk {
@@ -99,11 +99,15 @@ __device__ __forceinline__ void halo_epilogue(const IGemmArgs& p, const f32x4 (&
     return ((img + ii) * Ho + h) * Wo + w;
   };
 
-  // ---- plain bf16 output (no split, residual or second output; any
-  // activation but erf: the 3x3 convs of a bottleneck): bias and activation
+  // ---- plain bf16 output (the 3x3 convs of a bottleneck): bias and activation
   // in registers, the bf16 tile staged once (half the LDS bytes of the fp32
   // image), whole 16-B row chunks out.  Same arithmetic as epi_chunk (see
-  // cgemm_impl.h, the one-pass bf16 epilogue).
+  // cgemm_impl.h, the one-pass bf16 epilogue).  The guard is
+  // gemm::plain_bf16_epilogue(p) written out: as a call of that function the
+  // same seven terms cost the two 9-slot 64 x 64 tiles one more spilled SGPR
+  // each; and this block through one function shared with bgemm cost the two
+  // 256 x 64 fragment-prefetch tiles 4 and 8 more spilled VGPRs
+  // (docs/benchmarks.md, "One epilogue for the GEMM / conv kernels").
   if (p.splits <= 1 && p.residual == nullptr && p.out2 == nullptr && !p.out_f32 && p.out != nullptr &&
       p.act != kActGeluErf && !p.epi_f32) {
     constexpr int CB_LD = BN + 8;
@@ -117,7 +121,7 @@ __device__ __forceinline__ void halo_epilogue(const IGemmArgs& p, const f32x4 (&
       bj[j] = __uint_as_float(
           __builtin_amdgcn_raw_buffer_load_b32(rsb, uint32_t(n0 + wn * WN + j * 16 + fr) * 4u, 0, 0));
     const float alpha = p.alpha;
-    auto stage = [&](auto act_tag) __attribute__((always_inline)) {
+    dispatch_act<false>(p.act, [&](auto act_tag) __attribute__((always_inline)) {
       constexpr int ACT = decltype(act_tag)::value;
 #pragma unroll
       for (int i = 0; i < TM; ++i)
@@ -129,13 +133,7 @@ __device__ __forceinline__ void halo_epilogue(const IGemmArgs& p, const f32x4 (&
             Cb[(wm * WM + i * 16 + fq * 4 + r) * CB_LD + wn * WN + j * 16 + fr] =
                 __builtin_bit_cast(uint16_t, static_cast<__bf16>(v));
           }
-    };
-    switch (p.act) {
-      case kActRelu: stage(std::integral_constant<int, kActRelu>{}); break;
-      case kActGeluTanh: stage(std::integral_constant<int, kActGeluTanh>{}); break;
-      case kActTanh: stage(std::integral_constant<int, kActTanh>{}); break;
-      default: stage(std::integral_constant<int, kActNone>{}); break;
-    }
+    });
     __syncthreads();
     constexpr int CPRB = BN / 8;
 #pragma unroll 4
@@ -160,75 +158,18 @@ __device__ __forceinline__ void halo_epilogue(const IGemmArgs& p, const f32x4 (&
         Cs[(wm * WM + i * 16 + fq * 4 + r) * CS_LD + wn * WN + j * 16 + fr] = acc[i][j][r];
   __syncthreads();
 
-  using E = Epi<BM, BN, NT>;
   IGemmArgs q = p;                      // the epilogue's view (split-K fixup: splits 1, alpha 1)
   if (p.splits > 1) {
-    const float alpha = p.alpha;
-    float* ws = p.ws + size_t(blockIdx.y) * p.M * p.N;
-    const __amdgpu_buffer_rsrc_t wsr = splitk_rsrc(p);
-#pragma unroll 1
-    for (int it = 0; it < E::ITERS; ++it) {
-      int row, col;
-      if (!epi_rowcol<BM, BN, NT>(tid, it, row, col)) continue;
-      const int m = out_row(row), n = n0 + col;
-      if (m < 0 || n >= p.N) continue;
-      const float* src = Cs + row * CS_LD + col;
-      float4 a = *reinterpret_cast<const float4*>(src);
-      float4 b = *reinterpret_cast<const float4*>(src + 4);
-      a.x *= alpha; a.y *= alpha; a.z *= alpha; a.w *= alpha;
-      b.x *= alpha; b.y *= alpha; b.z *= alpha; b.w *= alpha;
-      float* dst = ws + size_t(m) * p.N + n;
-      if (p.counters != nullptr) {
-        splitk_store8(p, wsr, m, n, a, b);
-      } else {
-        *reinterpret_cast<float4*>(dst) = a;
-        *reinterpret_cast<float4*>(dst + 4) = b;
-      }
-    }
+    splitk_store_slab<BM, BN, NT, CS_LD, kSlabFixup | kSlabRolled>(p, Cs, n0, tid, out_row);
     if (p.counters == nullptr || !splitk_arrive(p, blockIdx.x)) {
       trace_stamp(p, 3);
       return;
     }
-    // the last slice of this tile: every slab summed back into Cs, then the
-    // epilogue below with the bias the split path did not prefetch
-    // (unrolled: every chunk's slab loads in flight together)
-#pragma unroll
-    for (int it = 0; it < E::ITERS; ++it) {
-      int row, col;
-      if (!epi_rowcol<BM, BN, NT>(tid, it, row, col)) continue;
-      const int m = out_row(row), n = n0 + col;
-      if (m < 0 || n >= p.N) continue;
-      float4 lo, hi;
-      splitk_sum8(p, wsr, m, n, lo, hi);
-      *reinterpret_cast<float4*>(Cs + row * CS_LD + col) = lo;
-      *reinterpret_cast<float4*>(Cs + row * CS_LD + col + 4) = hi;
-    }
-    __syncthreads();
-    q.splits = 1;
-    q.alpha = 1.f;                      // the slabs carry alpha already
-    prefetch_bias<BM, BN, NT>(q, n0, tid, bias0, bias1);
+    splitk_finish<BM, BN, NT, CS_LD>(q, Cs, n0, tid, out_row, bias0, bias1);
   }
-  const float bv[8] = {bias0.x, bias0.y, bias0.z, bias0.w, bias1.x, bias1.y, bias1.z, bias1.w};
-  auto run = [&](auto act_tag) {
-    constexpr int ACT = decltype(act_tag)::value;
-#pragma unroll 2
-    for (int it = 0; it < E::ITERS; ++it) {
-      int row, col;
-      if (!epi_rowcol<BM, BN, NT>(tid, it, row, col)) continue;
-      const int m = out_row(row), n = n0 + col;
-      if (m < 0 || n >= q.N) continue;
-      const uint4 rr = q.residual ? *reinterpret_cast<const uint4*>(q.residual + size_t(m) * q.ldr + n)
-                                  : make_uint4(0, 0, 0, 0);
-      epi_chunk<ACT>(q, Cs + row * CS_LD + col, m, n, bv, rr);
-    }
-  };
-  switch (q.act) {
-    case kActRelu: run(std::integral_constant<int, kActRelu>{}); break;
-    case kActGeluTanh: run(std::integral_constant<int, kActGeluTanh>{}); break;
-    case kActGeluErf: run(std::integral_constant<int, kActGeluErf>{}); break;
-    case kActTanh: run(std::integral_constant<int, kActTanh>{}); break;
-    default: run(std::integral_constant<int, kActNone>{}); break;
-  }
+  dispatch_act(q.act, [&](auto act) {
+    epilogue_rows<BM, BN, NT, CS_LD, decltype(act)::value, 2>(q, Cs, n0, tid, out_row, bias0, bias1);
+  });
 }
 
 template <int BM, int BN, int WGM, int WGN, int HR, int S, bool PF>
@@ -652,12 +593,7 @@ __global__ __launch_bounds__(512, 1) void halo_persist_kernel(IGemmArgs p, int n
                 __builtin_bit_cast(uint16_t, static_cast<__bf16>(v));
           }
     };
-    switch (p.act) {
-      case kActRelu: stage(std::integral_constant<int, kActRelu>{}); break;
-      case kActGeluTanh: stage(std::integral_constant<int, kActGeluTanh>{}); break;
-      case kActTanh: stage(std::integral_constant<int, kActTanh>{}); break;
-      default: stage(std::integral_constant<int, kActNone>{}); break;
-    }
+    dispatch_act<false>(p.act, stage);
     gemm::lds_barrier();
     {
       int r_ = t;
@@ -766,10 +702,10 @@ long persist_geometry(IGemmArgs& a) {
 hipError_t launch_halo_persist(const IGemmArgs& a0, hipStream_t s) {
   using G = HPs;
   IGemmArgs a = a0;
+  a.epi_f32 = epi_f32_env();   // (as the other launchers; the kernel does not read it: a forced fp32 epilogue is rejected below)
   // the configuration it is built for: one 64-channel chunk, 64 output
   // channels, plain bf16 output (see halo_persist_kernel)
-  if (a.C != KT || a.N != G::BN || a.splits > 1 || a.residual != nullptr || a.out2 != nullptr || a.out_f32 ||
-      a.out == nullptr || a.act == kActGeluErf || epi_f32_env() || a.counters != nullptr || a.ldc % 8)
+  if (a.C != KT || a.N != G::BN || !plain_bf16_epilogue(a) || a.counters != nullptr || a.ldc % 8)
     return hipErrorInvalidValue;
   if (long(a.M) * a.ldc * 2 >= 0x7fffffffL) return hipErrorInvalidValue;
   const long tiles = persist_geometry(a);

@@ -21,7 +21,7 @@
 //   * epilogue staged through LDS as fp32 so bias/residual/activation work on
 //     coalesced 16-B row chunks (residual read once, output written once).
 #include "common.h"
-#include "gemm_common.h"
+#include "gemm_epilogue.h"
 #include "launch.h"
 
 namespace tfsk {
@@ -60,62 +60,23 @@ struct IGemm {
   static constexpr int LDS = LDS_MAIN > LDS_EPI ? LDS_MAIN : LDS_EPI;
 };
 
-
-// s_waitcnt vmcnt(N) only (expcnt/lgkmcnt left at their maxima; gfx9 encoding:
-// vmcnt[3:0] + vmcnt[5:4] at bits 15:14, expcnt 6:4, lgkmcnt 11:8).
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-  static_assert(N >= 0 && N < 64, "vmcnt range");
-  __builtin_amdgcn_s_waitcnt((N & 15) | ((N >> 4) << 14) | (7 << 4) | (15 << 8));
-}
-
 // Workgroup barrier WITHOUT the vmcnt(0) drain that __syncthreads' fence
 // implies (that drain would empty the DMA ring every k-tile).  The "memory"
 // clobber keeps the compiler from moving LDS accesses across it; LDS reads
 // feeding MFMAs have already been waited on by then.
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_barrier" ::: "memory"); }
+// (A bare s_barrier: no lgkmcnt(0) wait, unlike gemm::lds_barrier -- see the note above that one.)
+__device__ __forceinline__ void lds_barrier_nowait() { asm volatile("s_barrier" ::: "memory"); }
 
-// Epilogue over the fp32 tile staged in LDS: coalesced 8-column row chunks,
-// alpha * acc + bias (+ residual) -> activation -> bf16 / f32 store.
-// Chunk `it` of this thread: row-major 8-column chunks, kThreads apart; since
-// kThreads is a multiple of the chunks per row, a thread's column never changes.
-template <int BM, int BN>
-struct EpiMap {
-  static constexpr int CPR = BN / 8;
-  static constexpr int ITERS = BM * CPR / kThreads;
-  static_assert(kThreads % CPR == 0 && (BM * CPR) % kThreads == 0, "epilogue chunk mapping");
-  static constexpr int PRE = ITERS <= 8 ? ITERS : 0;   // residual chunks prefetched into registers
-};
-
-template <int BM, int BN>
-__device__ __forceinline__ void epi_rowcol(int tid, int it, int& row, int& col) {
-  constexpr int CPR = BN / 8;
-  const int c = tid + it * kThreads;
-  row = c / CPR;
-  col = (c - row * CPR) * 8;
-}
-
-// Issue the residual loads of this thread's epilogue chunks early (before the
-// K loop) so their latency hides under the operand DMA and the MFMAs.
-template <int BM, int BN>
-__device__ __forceinline__ void prefetch_residual(const IGemmArgs& p, int m0, int n0, int tid,
-                                                  uint4 (&rpre)[EpiMap<BM, BN>::PRE > 0 ? EpiMap<BM, BN>::PRE : 1]) {
-  constexpr int PRE = EpiMap<BM, BN>::PRE;
-  if (PRE == 0 || !p.residual || p.splits > 1 || (p.N % 8) || (p.ldr % 8)) return;
-#pragma unroll
-  for (int it = 0; it < PRE; ++it) {
-    int row, col;
-    epi_rowcol<BM, BN>(tid, it, row, col);
-    const int m = m0 + row, n = n0 + col;
-    rpre[it] = (m < p.M && n + 8 <= p.N) ? *reinterpret_cast<const uint4*>(p.residual + size_t(m) * p.ldr + n)
-                                          : make_uint4(0, 0, 0, 0);
-  }
-}
-
+// Epilogue over the fp32 tile staged in LDS: coalesced 8-column row chunks
+// (gemm::Epi<BM, BN, kThreads>: kThreads is a multiple of the chunks per row,
+// so a thread's column never changes), alpha * acc + bias (+ residual) ->
+// activation -> bf16 / f32 store; a scalar path for N, ldc or ldr % 8 != 0,
+// which only this family is launched with.
 template <int BM, int BN, int CS_LD, int ACT>
 __device__ __forceinline__ void epilogue_rows(const IGemmArgs& p, const float* Cs, int m0, int n0, int tid,
-                                              const uint4 (&rpre)[EpiMap<BM, BN>::PRE > 0 ? EpiMap<BM, BN>::PRE : 1]) {
-  using EM = EpiMap<BM, BN>;
+                                              const uint4* rpre) {
+  using EM = gemm::Epi<BM, BN, kThreads>;
+  static_assert(EM::EXACT, "epilogue chunk mapping");
   const int M = p.M, N = p.N;
   const float alpha = p.alpha;
   const bool vec_ok = (N % 8 == 0) && (p.ldc % 8 == 0) && (!p.residual || p.ldr % 8 == 0);
@@ -123,7 +84,7 @@ __device__ __forceinline__ void epilogue_rows(const IGemmArgs& p, const float* C
   float bv[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   {
     int row0, col0;
-    epi_rowcol<BM, BN>(tid, 0, row0, col0);
+    gemm::epi_rowcol<BM, BN, kThreads>(tid, 0, row0, col0);
     const int n = n0 + col0;
     if (p.bias && vec_ok && n + 8 <= N) {
       const float4 b0 = *reinterpret_cast<const float4*>(p.bias + n);
@@ -138,7 +99,7 @@ __device__ __forceinline__ void epilogue_rows(const IGemmArgs& p, const float* C
   // instructions, far beyond the instruction cache)
   auto chunk = [&](int it, bool use_pre) {
     int row, col;
-    epi_rowcol<BM, BN>(tid, it, row, col);
+    gemm::epi_rowcol<BM, BN, kThreads>(tid, it, row, col);
     const int m = m0 + row, n = n0 + col;
     if (m >= M || n >= N) return;
     const float4 lo = *reinterpret_cast<const float4*>(Cs + row * CS_LD + col);
@@ -158,18 +119,7 @@ __device__ __forceinline__ void epilogue_rows(const IGemmArgs& p, const float* C
       }
 #pragma unroll
       for (int e = 0; e < 8; ++e) v[e] = act_fn<ACT>(v[e] * alpha + bv[e] + rv[e]);
-      if (p.out_f32) {
-        float* o = static_cast<float*>(p.out) + size_t(m) * p.ldc + n;
-        *reinterpret_cast<float4*>(o) = make_float4(v[0], v[1], v[2], v[3]);
-        *reinterpret_cast<float4*>(o + 4) = make_float4(v[4], v[5], v[6], v[7]);
-      } else {
-        uint16_t b[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) b[e] = f32_to_bf16(v[e]);
-        *reinterpret_cast<uint4*>(static_cast<uint16_t*>(p.out) + size_t(m) * p.ldc + n) =
-            make_uint4(b[0] | (uint32_t(b[1]) << 16), b[2] | (uint32_t(b[3]) << 16),
-                       b[4] | (uint32_t(b[5]) << 16), b[6] | (uint32_t(b[7]) << 16));
-      }
+      gemm::store_chunk(p, p.out, m, n, v);
     } else {
       for (int e = 0; e < 8 && n + e < N; ++e) {
         float x = v[e] * alpha;
@@ -471,8 +421,9 @@ __global__ __launch_bounds__(kThreads, 2) void igemm_kernel(IGemmArgs p) {
 #pragma unroll
     for (int j = 0; j < G::TN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  uint4 rpre[EpiMap<BM, BN>::PRE > 0 ? EpiMap<BM, BN>::PRE : 1];
-  prefetch_residual<BM, BN>(p, m0, n0, tid, rpre);
+  using EM = gemm::Epi<BM, BN, kThreads>;
+  uint4 rpre[EM::PRE > 0 ? EM::PRE : 1];
+  gemm::prefetch_residual<BM, BN, kThreads>(p, m0, n0, tid, rpre);
 
   const int nk_all = (K + BK - 1) / BK;
   const int kt0 = p.splits > 1 ? blockIdx.y * p.kt_per_split : 0;
@@ -511,14 +462,14 @@ __global__ __launch_bounds__(kThreads, 2) void igemm_kernel(IGemmArgs p) {
       // this wave's DMA of tile kt has landed once <= S-2 stages remain
       // outstanding; the barrier publishes every wave's DMA and guarantees all
       // waves are done reading tile kt-1, whose buffer the next DMA reuses
-      wait_vmcnt<(S - 2) * G::PER_STAGE>();
-      lds_barrier();
+      gemm::wait_vmcnt<(S - 2) * G::PER_STAGE>();
+      lds_barrier_nowait();
       const int nxt = kt + S - 1;
       gstage(nxt % S, kt0 + nxt, nxt < nk);
       const int cur = kt % S;
       mfma_tile(As + cur * BM * BK, Bs + cur * BN * BK);
     }
-    wait_vmcnt<0>();
+    gemm::wait_vmcnt<0>();
     __syncthreads();
   } else {
     gload(kt0);
@@ -544,38 +495,13 @@ __global__ __launch_bounds__(kThreads, 2) void igemm_kernel(IGemmArgs p) {
         Cs[(wm * G::WM + i * 16 + fq * 4 + r) * G::CS_LD + wn * G::WN + j * 16 + fr] = acc[i][j][r];
   __syncthreads();
 
-  const float alpha = p.alpha;
-  constexpr int CPR = BN / 8;   // chunks per row
-  if (p.splits > 1) {
-    // raw partial slab of this K split; splitk_reduce applies the epilogue
-    float* ws = p.ws + size_t(blockIdx.y) * M * N;
-    const bool v4 = (N % 4 == 0);
-    for (int c = tid; c < BM * CPR; c += kThreads) {
-      const int row = c / CPR, col = (c - row * CPR) * 8;
-      const int m = m0 + row, n = n0 + col;
-      if (m >= M || n >= N) continue;
-      const float* src = Cs + row * G::CS_LD + col;
-      float* dst = ws + size_t(m) * N + n;
-      if (v4 && n + 8 <= N) {
-        float4 a = *reinterpret_cast<const float4*>(src);
-        float4 b = *reinterpret_cast<const float4*>(src + 4);
-        a.x *= alpha; a.y *= alpha; a.z *= alpha; a.w *= alpha;
-        b.x *= alpha; b.y *= alpha; b.z *= alpha; b.w *= alpha;
-        *reinterpret_cast<float4*>(dst) = a;
-        *reinterpret_cast<float4*>(dst + 4) = b;
-      } else {
-        for (int e = 0; e < 8 && n + e < N; ++e) dst[e] = src[e] * alpha;
-      }
-    }
+  if (p.splits > 1) {   // splitk_reduce applies the epilogue (no in-kernel fixup in this family)
+    gemm::splitk_store_slab<BM, BN, kThreads, G::CS_LD, gemm::kSlabTail>(p, Cs, n0, tid, gemm::DenseRows{m0, M});
     return;
   }
-  switch (p.act) {
-    case kActRelu: epilogue_rows<BM, BN, G::CS_LD, kActRelu>(p, Cs, m0, n0, tid, rpre); break;
-    case kActGeluTanh: epilogue_rows<BM, BN, G::CS_LD, kActGeluTanh>(p, Cs, m0, n0, tid, rpre); break;
-    case kActGeluErf: epilogue_rows<BM, BN, G::CS_LD, kActGeluErf>(p, Cs, m0, n0, tid, rpre); break;
-    case kActTanh: epilogue_rows<BM, BN, G::CS_LD, kActTanh>(p, Cs, m0, n0, tid, rpre); break;
-    default: epilogue_rows<BM, BN, G::CS_LD, 0>(p, Cs, m0, n0, tid, rpre); break;
-  }
+  gemm::dispatch_act(p.act, [&](auto act) __attribute__((always_inline)) {
+    epilogue_rows<BM, BN, G::CS_LD, decltype(act)::value>(p, Cs, m0, n0, tid, rpre);
+  });
 }
 
 template <int BM, int BN, int AMODE, int NSTAGE, int WAVES_M = 2, int BKT = 64>

@@ -19,9 +19,17 @@ fine).  CPU only: hipcc -S --cuda-device-only.
 
     python scripts/isa_audit.py                       # every kernels/*.hip
     python scripts/isa_audit.py attention.hip stem.hip --kernel attention_kernel
+
+``--resources`` prints, instead, one line per kernel symbol with what the
+assembly's own metadata says of it (VGPRs, AGPRs, SGPRs, VGPR / SGPR spills,
+scratch bytes, static LDS bytes, occupancy, code bytes), its MFMA count and a
+digest of its instructions, compiled with the flags of ``_build.build_hip``:
+run it on two trees (absolute paths name another tree's files) and diff.
 """
 import argparse
+import concurrent.futures as cf
 import glob
+import hashlib
 import os
 import re
 import subprocess
@@ -43,9 +51,9 @@ SAVEEXEC = re.compile(r"^\s*s_and_saveexec_b64")
 RESTORE = re.compile(r"^\s*s_or_b64\s+exec,\s*exec")
 
 
-def compile_asm(src: str) -> str:
+def compile_asm(src: str, extra=()) -> str:
     out = tempfile.NamedTemporaryFile(suffix=".s", delete=False).name
-    cmd = [HIPCC, "-O3", "-std=c++17", "--offload-arch=gfx950", "-fno-gpu-rdc", "--cuda-device-only", "-S",
+    cmd = [HIPCC, "-O3", "-std=c++17", "--offload-arch=gfx950", "-fno-gpu-rdc", *extra, "--cuda-device-only", "-S",
            "-o", out, src]
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
@@ -126,13 +134,65 @@ def audit(body):
     return res
 
 
+RES_COLS = ("vgpr", "agpr", "sgpr", "vspill", "sspill", "scratch", "lds", "occ", "bytes", "mfma")
+INFO = {"NumVgprs": "vgpr", "NumAgprs": "agpr", "TotalNumSgprs": "sgpr", "ScratchSize": "scratch",
+        "LDSByteSize": "lds", "Occupancy": "occ", "codeLenInByte": "bytes"}
+
+
+def resources(asm: str):
+    """{symbol: {column: int, "code": digest of the instructions}} from the
+    '; Kernel info:' comments and the amdhsa.kernels metadata of one file."""
+    out = {}
+    for sym, body in kernels(asm):
+        code = [ln.split(";")[0].strip() for ln in body]
+        code = [ln for ln in code if ln and not ln.startswith(".")]
+        out[sym] = {"mfma": sum(bool(MFMA.match(ln)) for ln in code),
+                    "code": hashlib.sha1("\n".join(code).encode()).hexdigest()[:12]}
+    cur = meta = None
+    for ln in asm.splitlines():
+        m = re.match(r"^(_Z\w+):", ln)
+        if m:
+            cur = m.group(1) if m.group(1) in out else None
+        m = re.match(r"^; (\w+)\s*[:=]\s*(\d+)", ln)
+        if m and cur and m.group(1) in INFO:
+            out[cur][INFO[m.group(1)]] = int(m.group(2))
+        m = re.match(r"^\s+\.(name|sgpr_spill_count|vgpr_spill_count):\s+(\S+)", ln)
+        if m:   # amdhsa.kernels entry: keys in alphabetical order, so .name precedes both counts
+            if m.group(1) == "name":
+                meta = out.get(m.group(2))
+            elif meta is not None:
+                meta["sspill" if m.group(1) == "sgpr_spill_count" else "vspill"] = int(m.group(2))
+    for sym, r in out.items():
+        missing = [c for c in RES_COLS if c not in r]
+        if missing:   # a changed comment / metadata format must not print a table with holes
+            raise ValueError(f"{sym}: no {', '.join(missing)} in the assembly's kernel info / metadata")
+    return out
+
+
+def print_resources(files, only):
+    extra = ["-munsafe-fp-atomics"]          # as _build.build_hip compiles them
+    with cf.ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 1)) as ex:
+        asms = list(ex.map(lambda s: compile_asm(s, extra), files))
+    print("file symbol " + " ".join(RES_COLS) + " code")
+    for src, asm in zip(files, asms):
+        for sym, r in sorted(resources(asm).items()):
+            if only and only not in demangle(sym):
+                continue
+            print(os.path.basename(src), sym, " ".join(str(r[c]) for c in RES_COLS), r["code"])
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("files", nargs="*", help="kernel sources (default: every kernels/*.hip)")
     ap.add_argument("--kernel", default="", help="only symbols whose demangled name contains this")
     ap.add_argument("--all", action="store_true", help="also list kernels with no findings")
+    ap.add_argument("--resources", action="store_true",
+                    help="print each kernel's registers, spills, scratch, LDS, occupancy, code bytes and MFMA count "
+                         "(one line per symbol: diff two trees' tables) instead of the stall scan")
     a = ap.parse_args()
     files = [f if os.path.isabs(f) else os.path.join(KDIR, f) for f in a.files] or sorted(glob.glob(f"{KDIR}/*.hip"))
+    if a.resources:
+        return print_resources(files, a.kernel)
     for src in files:
         asm = compile_asm(src)
         for sym, body in kernels(asm):

@@ -81,3 +81,65 @@ def test_kernel_bodies_split_on_symbols():
     ])
     names = [sym for sym, _ in isa_audit.kernels(asm)]
     assert names == ["_Z3fooPf", "_Z3barPf"]
+
+
+# what hipcc -S emits around a kernel (a two-line kernel of this test's own, trimmed):
+# the body, the '; Kernel info:' comments and the amdhsa.kernels metadata entry
+RESOURCE_ASM = """
+	.protected	_Z1kPf
+_Z1kPf:
+; %bb.0:
+	s_load_dwordx2 s[0:1], s[0:1], 0x0
+	v_mfma_f32_16x16x32_bf16 a[0:3], v[2:5], v[6:9], a[0:3]
+	v_mfma_f32_16x16x32_bf16 a[0:3], v[2:5], v[6:9], a[0:3]
+	s_endpgm
+	.section	.rodata,"a",@progbits
+	.amdhsa_kernel _Z1kPf
+		.amdhsa_group_segment_fixed_size 256
+		.amdhsa_next_free_vgpr 3
+	.end_amdhsa_kernel
+.Lfunc_end0:
+; Kernel info:
+; codeLenInByte = 72
+; TotalNumSgprs: 8
+; NumVgprs: 3
+; NumAgprs: 4
+; TotalNumVgprs: 8
+; ScratchSize: 16
+; LDSByteSize: 256 bytes/workgroup (compile time only)
+; NumSGPRsForWavesPerEU: 8
+; Occupancy: 8
+amdhsa.kernels:
+  - .agpr_count:     4
+    .args:
+      - .address_space:  global
+        .name:           p
+        .offset:         0
+    .group_segment_fixed_size: 256
+    .name:           _Z1kPf
+    .private_segment_fixed_size: 16
+    .sgpr_count:     8
+    .sgpr_spill_count: 5
+    .symbol:         _Z1kPf.kd
+    .vgpr_count:     8
+    .vgpr_spill_count: 2
+"""
+
+
+def test_resources_reads_kernel_info_and_metadata():
+    r = isa_audit.resources(RESOURCE_ASM)
+    assert list(r) == ["_Z1kPf"]
+    k = r["_Z1kPf"]
+    assert {c: k[c] for c in isa_audit.RES_COLS} == {
+        "vgpr": 3, "agpr": 4, "sgpr": 8, "vspill": 2, "sspill": 5, "scratch": 16, "lds": 256, "occ": 8,
+        "bytes": 72, "mfma": 2}
+    # the digest covers the instructions only: comments and directives do not move it
+    same = isa_audit.resources(RESOURCE_ASM.replace("; %bb.0:", "; %bb.0: entry"))["_Z1kPf"]["code"]
+    other = isa_audit.resources(RESOURCE_ASM.replace("s[0:1], 0x0", "s[0:1], 0x8"))["_Z1kPf"]["code"]
+    assert same == k["code"] and other != k["code"]
+
+
+def test_resources_refuses_a_table_with_holes():
+    import pytest
+    with pytest.raises(ValueError, match="vspill"):
+        isa_audit.resources(RESOURCE_ASM.replace("    .vgpr_spill_count: 2\n", ""))
