@@ -9,6 +9,10 @@ a single consumer and is not fetched):
   explicit padding, residual add + ReLU in the MFMA kernel's epilogue.  A conv
   whose input has C % 8 != 0 (the RGB stem) reads the fp32 request tensor
   directly (ingest cast fused into the operand loads).
+* ``[Pad] -> DepthwiseConv2dNative -> [BiasAdd] -> [FusedBatchNorm*] -> [Relu|Relu6]``
+  => ``_FusedDepthwiseConv2D`` (channel multiplier 1): BN folded into the fp32
+  filter, one ``dwconv2d`` launch (kernels/dwconv.hip).  ``Relu6`` also fuses
+  into ``_FusedConv2D`` (MobileNet's pointwise convs).
 * ``MatMul -> [BiasAdd] -> [Add(residual)] -> [Relu|Tanh|GELU]`` => ``_FusedMatMul``
   (fp32 output when it feeds a Softmax/ArgMax head or is fetched).
 * ``Mean(NHWC, axes=[1,2])`` => ``_GlobalAvgPool``;  ``MaxPool`` => ``_MaxPool``;
@@ -163,7 +167,8 @@ class FusedConv:
     def post_ok(self) -> bool:
         """The fused kernels write the post output only on the cgemm / halo
         paths (64-aligned channels); the CPU reference always can."""
-        return not self.use_hip or (not self.c4 and self.cin % 64 == 0 and self.cout % 8 == 0)
+        return not self.use_hip or (not self.c4 and self.cin % 64 == 0 and self.cout % 8 == 0 and
+                                    self.act != "relu6")      # (the post output is cgemm / halo only; they have no relu6)
 
     def pads_for(self, h, w):
         if self.padding == "SAME":
@@ -223,10 +228,68 @@ class FusedConv:
             (("nohalo",) if halo_shape and self.sw == 1 and not halo else ())
         kw_post, outs = _post_kwargs(self, out)
         run = lambda c, s: H.conv2d(*args, cfg=c, out=out, splits=s, **kw_post)  # noqa
+        # (ReLU6 is an igemm epilogue only: those launches tune over the igemm configs)
+        flags = {"relu6": True} if self.act == "relu6" else {}
         cfg, splits = tuned_config(key, M, self.cout, run, K, dma, aligned, halo=halo,
-                                   cgemm_only=self.post is not None, stem=self.c4)
+                                   cgemm_only=self.post is not None, stem=self.c4, **flags)
         run(cfg, splits)
         return outs
+
+
+class FusedDepthwiseConv:
+    """DepthwiseConv2dNative (channel multiplier 1)(+folded BN/bias)(+act).
+    The filter stays fp32 on both paths: [KH][KW][C], which the kernel reads as
+    [KH*KW][C] (9 C floats for a 3x3: rounding it to bf16 would cost 2^-9
+    relative error for no saving)."""
+
+    MAX_K = 7                       # kernels/dwconv.hip kMaxTaps
+
+    def __init__(self, w_hwc: torch.Tensor, bias: torch.Tensor, strides, padding: str, pads, act: str,
+                 device: torch.device, use_hip: bool, name: str):
+        self.kh, self.kw, self.c = w_hwc.shape
+        self.sh, self.sw = strides
+        self.padding = padding          # "SAME" | "VALID" | "EXPLICIT"
+        self.pads = pads                # (pt, pb, pl, pr) for EXPLICIT
+        self.act = act
+        self.use_hip = use_hip
+        self.name = name
+        self.device = device
+        self.w = to_device(w_hwc.float().contiguous(), device)
+        self.b = to_device(bias.float(), device)
+
+    @classmethod
+    def hip_ok(cls, kh: int, kw: int, c: int) -> bool:
+        return c % 8 == 0 and kh <= cls.MAX_K and kw <= cls.MAX_K
+
+    pads_for = FusedConv.pads_for
+
+    def __call__(self, ctx, node, ins):
+        x = O.to_torch(ins[0])
+        pt, pb, pl, pr = self.pads_for(x.shape[1], x.shape[2])
+        n, h, w, _ = x.shape
+        ho = (h + pt + pb - self.kh) // self.sh + 1
+        wo = (w + pl + pr - self.kw) // self.sw + 1
+        if not self.use_hip:
+            wt = self.w.to(x.device).permute(2, 0, 1).reshape(self.c, 1, self.kh, self.kw)
+            y = F.conv2d(F.pad(x.float().permute(0, 3, 1, 2), [pl, pr, pt, pb]), wt, stride=(self.sh, self.sw),
+                         groups=self.c)
+            y = y.permute(0, 2, 3, 1) + self.b.to(x.device)
+            return [_ref_act(y, self.act).contiguous()]
+        from ..ops import ACT, hip, tuned_choice
+        H = hip()
+        x = _to_bf16(x).contiguous()
+        out = torch.empty((n, ho, wo, self.c), device=x.device, dtype=BF16)
+
+        def run(strip):
+            return H.dwconv2d(x, self.w, self.b, self.kh, self.kw, self.sh, self.sw, pt, pl, ho, wo, ACT[self.act],
+                              out, strip)
+        auto = H.dwconv_strip(n, ho, wo, self.c, self.kh, self.kw, self.sh, self.sw)
+        if auto == 0:
+            return [run(0)]         # the generic kernel has one form
+        # output rows per thread (kernels/launch.h kDwStripShort / kDwStripTall), timed per shape
+        key = ("dwconv", tuple(x.shape), self.kh, self.kw, self.sh, self.sw, pt, pl, ho, wo, self.act)
+        pick = tuned_choice(key, {2: lambda: run(2), 8: lambda: run(8)}, default=auto)
+        return [run(pick)]
 
 
 class FusedDualConv:
@@ -699,6 +762,8 @@ def _post_kwargs(impl, out: torch.Tensor):
 def _ref_act(y, act):
     if act == "relu":
         return torch.relu(y)
+    if act == "relu6":
+        return torch.clamp(y, 0.0, 6.0)
     if act == "tanh":
         return torch.tanh(y)
     if act == "gelu_tanh":
@@ -712,7 +777,7 @@ def _impl_op(ctx, node, ins):
     return node.attrs["_impl"](ctx, node, ins)
 
 
-for _op in ("_FusedConv2D", "_FusedDualConv", "_FusedMatMul", "_GlobalAvgPool", "_MaxPool",
+for _op in ("_FusedConv2D", "_FusedDepthwiseConv2D", "_FusedDualConv", "_FusedMatMul", "_GlobalAvgPool", "_MaxPool",
             "_SoftmaxArgMax", "_LayerNorm",
             "_FusedQKV", "_Attention", "_EmbeddingLN", "_KeyMaskAdder", "_DenseSoftmax"):
     O.OPS[_op] = _impl_op
@@ -1131,13 +1196,85 @@ def fuse_conv(g, order, fed, fetch_refs, device, opts):
                 chain.append(nxt)
                 cur = nxt
                 nxt = c.only_consumer(cur.name)
-        if nxt is not None and nxt.op == "Relu":
-            act = "relu"
+        if nxt is not None and nxt.op in ("Relu", "Relu6"):
+            act = nxt.op.lower()
             chain.append(nxt)
             cur = nxt
         impl = FusedConv(w, bias, (strides[1], strides[2]), padding, pads, act, device, c.use_hip, cur.name)
         inputs = [x_ref] + ([residual] if residual is not None else [])
         _finalize(g, chain, "_FusedConv2D", inputs, {"_impl": impl})
+        c.refresh()
+
+
+def fuse_depthwise(g, order, fed, fetch_refs, device, opts):
+    """``[Pad ->] DepthwiseConv2dNative [-> BiasAdd] [-> FusedBatchNorm*] [-> Relu | Relu6]``
+    -> ``_FusedDepthwiseConv2D``, under fuse_conv's guards (NHWC, dilation 1, a
+    constant 4-D filter, an inference BatchNorm whose only used output is y, no
+    fetch inside the chain, single consumers) and channel multiplier 1.  On the
+    GPU also C % 8 == 0 and a filter of at most 7 x 7 (kernels/dwconv.hip);
+    anything else stays on the reference op."""
+    c = _Ctx(g, order, fed, fetch_refs, device, opts)
+    for name in order:
+        n = g.nodes.get(name)
+        if n is None or n.op != "DepthwiseConv2dNative" or n.sattr("data_format", "NHWC") != "NHWC":
+            continue
+        dil = n.attr("dilations", [1, 1, 1, 1]) or [1, 1, 1, 1]
+        if any(d != 1 for d in dil):
+            continue
+        w = _const(g, n.inputs[1])
+        if w is None or w.dim() != 4 or w.shape[3] != 1:
+            continue
+        kh, kw, ch, _mult = w.shape
+        if c.use_hip and not FusedDepthwiseConv.hip_ok(kh, kw, ch):
+            continue
+        x_ref = n.inputs[0]
+        padding = n.sattr("padding", "VALID")
+        pads = (0, 0, 0, 0)
+        chain: List[Node] = []
+        if padding == "EXPLICIT":
+            ep = n.attr("explicit_paddings", [])
+            if ep[0] or ep[1] or ep[6] or ep[7]:
+                continue
+            pads = (ep[2], ep[3], ep[4], ep[5])
+        prod = g.nodes.get(x_ref[0])
+        if (padding == "VALID" and prod is not None and prod.op == "Pad" and x_ref[1] == 0
+                and c.only_consumer(prod.name) is n):
+            pv = _const(g, prod.inputs[1])
+            if pv is not None:
+                p = [int(v) for v in pv.reshape(-1).tolist()]
+                if p[0] == p[1] == p[6] == p[7] == 0 and min(p) >= 0:
+                    chain.append(prod)
+                    x_ref = prod.inputs[0]
+                    padding, pads = "EXPLICIT", (p[2], p[3], p[4], p[5])
+        strides = n.attr("strides", [1, 1, 1, 1])
+        w = w.float().reshape(kh, kw, ch)
+        bias = zeros(ch, w)
+        chain.append(n)
+        cur = n
+        act = "none"
+        nxt = c.only_consumer(cur.name)
+        if nxt is not None and nxt.op == "BiasAdd" and nxt.inputs[0] == (cur.name, 0):
+            b = _const(g, nxt.inputs[1])
+            if b is not None and b.numel() == ch:
+                bias = bias + b.float()
+                chain.append(nxt)
+                cur = nxt
+                nxt = c.only_consumer(cur.name)
+        if (nxt is not None and nxt.op in ("FusedBatchNorm", "FusedBatchNormV2", "FusedBatchNormV3")
+                and nxt.inputs[0] == (cur.name, 0)):
+            aff = _bn_affine(g, c, nxt)
+            if aff is not None and aff[0].numel() == ch:
+                w = w * aff[0]
+                bias = bias * aff[0] + aff[1]
+                chain.append(nxt)
+                cur = nxt
+                nxt = c.only_consumer(cur.name)
+        if nxt is not None and nxt.op in ("Relu", "Relu6"):
+            act = nxt.op.lower()
+            chain.append(nxt)
+            cur = nxt
+        impl = FusedDepthwiseConv(w, bias, (strides[1], strides[2]), padding, pads, act, device, c.use_hip, cur.name)
+        _finalize(g, chain, "_FusedDepthwiseConv2D", [x_ref], {"_impl": impl})
         c.refresh()
 
 
@@ -1284,6 +1421,8 @@ def fuse_dual_conv(g, order, fed, fetch_refs, device, opts):
         b = r.attrs["_impl"]
         if not (_is_1x1(a) and _is_1x1(b)) or b.act != "none" or c.only_consumer(r.name) is not n:
             continue
+        if a.act == "relu6":
+            continue                  # the dual conv is cgemm-only, and cgemm has no relu6
         if a.cin % 64 or b.cin % 64 or a.cout != b.cout or a.cout % 8:
             continue
         # the stride-1 conv's input is the dense source (its rows are the output pixels)
@@ -1425,7 +1564,7 @@ def fuse_conv_chain(g, order, fed, fetch_refs, device, opts):
 
 def default_passes(options=None):
     from .patterns import bert_passes, late_passes
-    return [fuse_pools, fuse_softmax_argmax] + bert_passes() + [fuse_conv, fuse_dual_conv, fuse_post_activation,
+    return [fuse_pools, fuse_softmax_argmax] + bert_passes() + [fuse_conv, fuse_depthwise, fuse_dual_conv, fuse_post_activation,
                                                                  fuse_stem_pool, fuse_matmul,
                                                                  fuse_classifier_head, fuse_dense_softmax,
                                                                  fuse_conv_chain] + late_passes() + \

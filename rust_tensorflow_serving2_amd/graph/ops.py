@@ -621,6 +621,8 @@ def _conv2d(ctx, n, ins):
 @op("DepthwiseConv2dNative")
 def _dwconv(ctx, n, ins):
     x, w = _same_device(to_torch(ins[0]), to_torch(ins[1]))
+    if w.dtype != x.dtype and x.is_floating_point():
+        w = w.to(x.dtype)       # a bf16 activation from a fused op against the fp32 filter constant
     strides = n.attr("strides", [1, 1, 1, 1])
     nhwc = _nhwc(n, x)
     xc = x.permute(0, 3, 1, 2) if nhwc else x

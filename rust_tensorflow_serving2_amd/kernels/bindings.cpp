@@ -10,6 +10,7 @@
 #include <ATen/hip/impl/HIPGuardImplMasqueradingAsCUDA.h>
 #include <ATen/hip/impl/HIPStreamMasqueradingAsCUDA.h>
 
+#include "common.h"
 #include "launch.h"
 #include "cgemm.h"
 
@@ -127,6 +128,29 @@ bool aligned16(const Tensor& t) { return reinterpret_cast<uintptr_t>(t.data_ptr(
 
 const uint16_t* bf16p(const Tensor& t) { return reinterpret_cast<const uint16_t*>(t.data_ptr()); }
 
+// An activation code the kernels do not implement is an error, never "none"
+// (their switches send unknown codes to the default case).  Every GEMM / conv
+// family implements the codes up to kActTanh.  ReLU6 is built into igemm
+// (which takes every shape) and the split-K reduce only: with the extra case
+// in their epilogue switches 61 of the cgemm kernels spilled more registers
+// (profiles/dwconv/resources_before_after.txt), and bgemm and halo are kept
+// byte-identical for the ResNet / BERT engines.  A relu6 launch on one of
+// their configs is rejected here, and ops.candidates(relu6=True) offers igemm
+// configs only.  The deferred-LayerNorm epilogue has no ReLU6 either, and the
+// post-activation outputs (act2, the max-pool's) are none / ReLU only.
+bool relu6_cfg(int64_t cfg) {
+  return config_of(cfg) != nullptr && config_of(cfg)->family == tfsk::TileFamily::kIGemm;
+}
+void need_act(int64_t act, int64_t cfg, const char* op) {
+  TORCH_CHECK(act >= tfsk::kActNone && act <= tfsk::kActRelu6, op, ": unknown activation code ", act);
+  TORCH_CHECK(act != tfsk::kActRelu6 || config_of(cfg) == nullptr || relu6_cfg(cfg), op,
+              ": activation relu6 is built into the igemm kernels only (tile config ", cfg, " is not one)");
+}
+void need_post_act(int64_t act, const char* op) {
+  TORCH_CHECK(act == tfsk::kActNone || act == tfsk::kActRelu, op, ": the post activation is none (0) or relu (1), got ",
+              act);
+}
+
 // Post-activation output (ResNet v2): out2 = act2(y * scale + shift) per output
 // channel, written by the same GEMM epilogue.  post_only: `y` itself receives
 // the post-activated values (the raw sum is not stored).  cgemm / halo configs
@@ -139,6 +163,7 @@ void set_post(tfsk::IGemmArgs& a, const c10::optional<Tensor>& scale, const c10:
     return;
   }
   TORCH_CHECK(shift.has_value(), "post_scale needs post_shift");
+  need_post_act(act2, "conv");
   need(*scale, at::kFloat, "post_scale");
   need(*shift, at::kFloat, "post_shift");
   TORCH_CHECK(scale->numel() == cout && shift->numel() == cout, "post scale / shift must have Cout entries");
@@ -169,6 +194,7 @@ Tensor conv2d(const Tensor& x, const Tensor& w, const c10::optional<Tensor>& bia
               const c10::optional<Tensor>& post_scale, const c10::optional<Tensor>& post_shift, int64_t post_act,
               const c10::optional<Tensor>& out2, bool post_only) {
   const bool stem = x.scalar_type() == at::kFloat;
+  need_act(act, cfg, "conv2d");
   need(x, stem ? at::kFloat : at::kBFloat16, "x");
   need(w, at::kBFloat16, "w");
   TORCH_CHECK(x.dim() == 4, "x must be NHWC");
@@ -228,6 +254,7 @@ Tensor conv2d_dual(const Tensor& h, const Tensor& x, const Tensor& w, const c10:
                    int64_t SH, int64_t SW, int64_t act, int64_t cfg, const c10::optional<Tensor>& out, int64_t splits,
                    const c10::optional<Tensor>& post_scale, const c10::optional<Tensor>& post_shift,
                    int64_t post_act, const c10::optional<Tensor>& out2, bool post_only) {
+  need_act(act, cfg, "conv2d_dual");
   need(h, at::kBFloat16, "h");
   need(x, at::kBFloat16, "x");
   need(w, at::kBFloat16, "w");
@@ -268,6 +295,7 @@ Tensor linear(const Tensor& x, const Tensor& w, const c10::optional<Tensor>& bia
               const c10::optional<Tensor>& out, int64_t splits) {
   // x: contiguous, or a row-strided 2-D view (x[r][k] at r * lda + k; e.g.
   // BERT's pooler reads every sequence's first token straight from [B, S, H])
+  need_act(act, cfg, "linear");
   const bool strided = !x.is_contiguous();
   if (strided) {
     TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16 && x.dim() == 2 && x.stride(1) == 1 &&
@@ -325,6 +353,8 @@ std::vector<Tensor> linear_lnx(const Tensor& x, const Tensor& w, const c10::opti
                                const c10::optional<Tensor>& a_colsum, double a_eps,
                                const c10::optional<Tensor>& r_st, const c10::optional<Tensor>& r_gamma,
                                const c10::optional<Tensor>& r_beta, double r_eps, bool stats) {
+  TORCH_CHECK(act >= tfsk::kActNone && act <= tfsk::kActTanh, "linear_lnx: unknown activation code ", act,
+              " (the deferred-LayerNorm epilogue has no relu6)");
   need(x, at::kBFloat16, "x");
   need(w, at::kBFloat16, "w");
   c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
@@ -443,6 +473,7 @@ Tensor maxpool(const Tensor& x, int64_t KH, int64_t KW, int64_t SH, int64_t SW, 
   const float* sh = nullptr;
   if (post_scale.has_value()) {
     TORCH_CHECK(post_shift.has_value(), "post_scale needs post_shift");
+    need_post_act(post_act, "maxpool");
     need(*post_scale, at::kFloat, "post_scale");
     need(*post_shift, at::kFloat, "post_shift");
     TORCH_CHECK(post_scale->numel() == C && post_shift->numel() == C, "post scale / shift must have C entries");
@@ -451,6 +482,44 @@ Tensor maxpool(const Tensor& x, int64_t KH, int64_t KW, int64_t SH, int64_t SW, 
   }
   check(tfsk::maxpool_nhwc_launch(bf16p(x), bf16p_mut(y), N, H, W, C, KH, KW, SH, SW, PT, PL, Ho, Wo,
                                   cur_stream(x), sc, sh, int(post_act)), "maxpool");
+  return y;
+}
+
+// Depthwise conv (dwconv.hip): x NHWC bf16 (C % 8 == 0), w [KH*KW][C] f32 (BatchNorm
+// folded in), bias [C] f32 -> act(conv + bias) as [N][Ho][Wo][C] bf16.  Top /
+// left padding and the output size come from the caller (SAME / VALID /
+// explicit padding all reduce to them); taps outside the image read zero.
+Tensor dwconv2d(const Tensor& x, const Tensor& w, const Tensor& bias, int64_t KH, int64_t KW, int64_t SH, int64_t SW,
+                int64_t PT, int64_t PL, int64_t Ho, int64_t Wo, int64_t act, const c10::optional<Tensor>& out,
+                int64_t strip) {
+  TORCH_CHECK(act == tfsk::kActNone || act == tfsk::kActRelu || act == tfsk::kActRelu6,
+              "dwconv2d: the activation is none (0), relu (1) or relu6 (5), got ", act);
+  need(x, at::kBFloat16, "x");
+  need(w, at::kFloat, "w");
+  need(bias, at::kFloat, "bias");
+  TORCH_CHECK(x.dim() == 4 && x.size(3) > 0 && x.size(3) % 8 == 0, "dwconv2d: NHWC with C % 8 == 0 (got ",
+              x.dim() == 4 ? x.size(3) : -1, " channels)");
+  TORCH_CHECK(KH >= 1 && KW >= 1 && KH <= 7 && KW <= 7, "dwconv2d: filters up to 7 x 7 (got ", KH, " x ", KW, ")");
+  TORCH_CHECK(SH >= 1 && SW >= 1 && PT >= 0 && PL >= 0 && Ho >= 1 && Wo >= 1, "dwconv2d: bad geometry");
+  const int64_t N = x.size(0), H = x.size(1), W = x.size(2), C = x.size(3);
+  TORCH_CHECK(H >= 1 && W >= 1, "dwconv2d: empty image");
+  // the last window must start inside the padded image: no output made of padding alone
+  TORCH_CHECK((Ho - 1) * SH - PT < H && (Wo - 1) * SW - PL < W, "dwconv2d: output larger than the input allows");
+  TORCH_CHECK(w.numel() == KH * KW * C, "dwconv2d: w must be [KH*KW][C] (channel multiplier 1)");
+  TORCH_CHECK(bias.numel() == C, "dwconv2d: bias must have C entries");
+  TORCH_CHECK(w.device() == x.device() && bias.device() == x.device(), "dwconv2d: tensors on different devices");
+  TORCH_CHECK(strip == 0 || strip == tfsk::kDwStripShort || strip == tfsk::kDwStripTall, "dwconv2d: strip must be 0, ",
+              tfsk::kDwStripShort, " or ", tfsk::kDwStripTall);
+  TORCH_CHECK(x.numel() * 2 < 0x7ffffff0LL && N * Ho * Wo * C * 2 < 0x7ffffff0LL, "dwconv2d operands must be < 2 GiB");
+  TORCH_CHECK(Wo * (C / 8) <= 65535LL * 256, "dwconv2d: output rows of more than 16 M chunks");
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
+  Tensor y = out.has_value() ? *out : torch::empty({N, Ho, Wo, C}, x.options());
+  need(y, at::kBFloat16, "out");
+  TORCH_CHECK(y.numel() == N * Ho * Wo * C && y.device() == x.device(), "out has the wrong size");
+  TORCH_CHECK(aligned16(x) && aligned16(w) && aligned16(bias) && aligned16(y), "dwconv2d: tensors must be 16-B aligned");
+  check(tfsk::dwconv_nhwc_launch(bf16p(x), w.data_ptr<float>(), bias.data_ptr<float>(), bf16p_mut(y), int(N), int(H),
+                                 int(W), int(C), int(KH), int(KW), int(SH), int(SW), int(PT), int(PL), int(Ho), int(Wo),
+                                 int(act), int(strip), cur_stream(x)), "dwconv2d");
   return y;
 }
 
@@ -888,6 +957,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("maxpool", &maxpool, py::arg("x"), py::arg("kh"), py::arg("kw"), py::arg("sh"), py::arg("sw"),
         py::arg("pt"), py::arg("pb"), py::arg("pl"), py::arg("pr"), py::arg("out") = py::none(),
         py::arg("post_scale") = py::none(), py::arg("post_shift") = py::none(), py::arg("post_act") = 0);
+  m.def("dwconv2d", &dwconv2d, "depthwise conv: act(conv(x, w [KH*KW][C] f32) + bias), NHWC bf16", py::arg("x"),
+        py::arg("w"), py::arg("bias"), py::arg("kh"), py::arg("kw"), py::arg("sh"), py::arg("sw"), py::arg("pt"),
+        py::arg("pl"), py::arg("ho"), py::arg("wo"), py::arg("act") = 0, py::arg("out") = py::none(),
+        py::arg("strip") = 0);
+  m.def("dwconv_strip", [](int64_t n, int64_t ho, int64_t wo, int64_t c, int64_t kh, int64_t kw, int64_t sh,
+                           int64_t sw) {
+    return tfsk::dwconv_strip(int(n), int(ho), int(wo), int(c), int(kh), int(kw), int(sh), int(sw));
+  }, "output rows per thread dwconv2d picks by itself (0: the generic kernel, which has no strips)");
   m.def("global_avgpool", &global_avgpool, py::arg("x"), py::arg("out") = py::none());
   m.def("classifier_head", &classifier_head, "softmax/argmax(mean_hw(x) @ w^T + bias)[:, :n]", py::arg("x"),
         py::arg("w"), py::arg("bias"), py::arg("n"));
@@ -961,6 +1038,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("classifier_head_one_launch", [](int64_t M, int64_t HW, int64_t K, int64_t Np, int64_t n) {
     return tfsk::classifier_head_one_launch(int(M), int(HW), int(K), int(Np), int(n));
   });
+  m.def("relu6_config", [](int64_t cfg) { return relu6_cfg(cfg); },
+        "whether the tile config's kernels implement activation relu6 (the igemm ones do)");
   m.def("num_configs", []() { return tfsk::kNumIGemmConfigs; });
   // (in the order of the rows of tile_configs.h; the GPU tests parametrize over them)
   auto ids_where = [](bool (*in_family)(tfsk::TileFamily)) {

@@ -15,7 +15,8 @@ typedef uint16_t bf16_t;   // storage type on the host-visible side
 constexpr int kWave = 64;
 constexpr int kNumXcd = 8;
 
-enum Act : int { kActNone = 0, kActRelu = 1, kActGeluTanh = 2, kActGeluErf = 3, kActTanh = 4 };
+enum Act : int { kActNone = 0, kActRelu = 1, kActGeluTanh = 2, kActGeluErf = 3, kActTanh = 4,
+                 kActRelu6 = 5 };
 
 __device__ __forceinline__ float bf16_to_f32(bf16_t v) {
   return __uint_as_float(uint32_t(v) << 16);
@@ -52,6 +53,7 @@ __device__ __forceinline__ float apply_act(float x, int act) {
     case kActGeluTanh: return gelu_tanh(x);
     case kActGeluErf: return 0.5f * x * (1.f + erff(x * 0.7071067811865476f));
     case kActTanh: return 2.f * sigm2(x) - 1.f;
+    case kActRelu6: return fminf(fmaxf(x, 0.f), 6.f);
     default: return x;
   }
 }
@@ -68,6 +70,8 @@ __device__ __forceinline__ float act_fn(float x) {
     return 0.5f * x * (1.f + erff(x * 0.7071067811865476f));
   } else if constexpr (ACT == kActTanh) {
     return 2.f * sigm2(x) - 1.f;
+  } else if constexpr (ACT == kActRelu6) {
+    return fminf(fmaxf(x, 0.f), 6.f);
   } else {
     return x;
   }

@@ -499,7 +499,7 @@ __global__ __launch_bounds__(kThreads, 2) void igemm_kernel(IGemmArgs p) {
     gemm::splitk_store_slab<BM, BN, kThreads, G::CS_LD, gemm::kSlabTail>(p, Cs, n0, tid, gemm::DenseRows{m0, M});
     return;
   }
-  gemm::dispatch_act(p.act, [&](auto act) __attribute__((always_inline)) {
+  gemm::dispatch_act<true, true>(p.act, [&](auto act) __attribute__((always_inline)) {
     epilogue_rows<BM, BN, G::CS_LD, decltype(act)::value>(p, Cs, m0, n0, tid, rpre);
   });
 }

@@ -164,6 +164,18 @@ hipError_t maxpool_nhwc_launch(const uint16_t* x, uint16_t* y, int N, int H, int
                                int KH, int KW, int SH, int SW, int PT, int PL, int Ho, int Wo,
                                hipStream_t stream, const float* scale = nullptr, const float* shift = nullptr,
                                int act = 0);
+// NHWC bf16 depthwise conv, channel multiplier 1 (dwconv.hip): x [N][H][W][C]
+// (C % 8 == 0), w [KH*KW][C] f32, bias [C] f32 -> y [N][Ho][Wo][C] bf16 =
+// act(conv + bias), act in {kActNone, kActRelu, kActRelu6}; KH, KW <= 7,
+// explicit top / left padding, Ho / Wo from the caller (taps outside the image
+// read zero).  3x3 with stride 1 or 2 runs the strip kernels, `strip` output
+// rows per thread (kDwStripShort, kDwStripTall, or 0: dwconv_strip's rule);
+// anything else the generic kernel.  Operands must be < 2 GiB.
+constexpr int kDwStripShort = 2, kDwStripTall = 8;
+int dwconv_strip(int N, int Ho, int Wo, int C, int KH, int KW, int SH, int SW, int strip = 0);
+hipError_t dwconv_nhwc_launch(const uint16_t* x, const float* w, const float* bias, uint16_t* y, int N, int H, int W,
+                              int C, int KH, int KW, int SH, int SW, int PT, int PL, int Ho, int Wo, int act,
+                              int strip, hipStream_t stream);
 // Mean over H,W of NHWC bf16 -> [N][C] (bf16).
 hipError_t global_avgpool_nhwc_launch(const uint16_t* x, uint16_t* y, int N, int HW, int C,
                                       hipStream_t stream);

@@ -51,7 +51,7 @@ def available() -> bool:
         return False
 
 
-ACT = {"none": 0, "relu": 1, "gelu_tanh": 2, "gelu_erf": 3, "tanh": 4}
+ACT = {"none": 0, "relu": 1, "gelu_tanh": 2, "gelu_erf": 3, "tanh": 4, "relu6": 5}   # kernels/common.h Act
 
 # ------------------------------------------------------------------ autotune
 _TUNED: Dict[Tuple, int] = {}
@@ -193,7 +193,8 @@ def heuristic_splits(M: int, N: int, K: int, cfg: int) -> int:
 
 
 def candidates(M: int, N: int, K: int, dma: bool = True, aligned64: bool = False, cgemm_only: bool = False,
-               halo: bool = False, no_split: bool = False, stem: bool = False, ln: bool = False):
+               halo: bool = False, no_split: bool = False, stem: bool = False, ln: bool = False,
+               relu6: bool = False):
     """(tile config, split-K) pairs worth timing for an M x N x K problem
     (``dma``: the operand mode uses the direct-to-LDS path, so the deeper
     DMA-ring configs apply; ``aligned64``: K and the conv channels are
@@ -201,10 +202,11 @@ def candidates(M: int, N: int, K: int, dma: bool = True, aligned64: bool = False
     stride-1 conv with C % 64 == 0, so the halo-tiled configs apply too —
     their split-K granule is a 64-channel chunk of 9 taps; ``stem``: the
     padded RGBA stem operand, which the 32-deep and persistent builds do not
-    take)."""
+    take; ``relu6``: the launch's activation is ReLU6, which only the igemm
+    kernels implement)."""
     nk = -(-K // 64)
     out = []
-    if halo and aligned64 and K % 576 == 0 and N % 8 == 0:
+    if halo and aligned64 and K % 576 == 0 and N % 8 == 0 and not relu6:
         nch = K // 576
         for cfg, (bm, bn) in HALO.items():
             if bn > 64 and N <= bn // 2:
@@ -227,6 +229,8 @@ def candidates(M: int, N: int, K: int, dma: bool = True, aligned64: bool = False
             continue
         if cgemm_only and cfg not in CGEMM:
             continue
+        if relu6 and cfg in CGEMM:
+            continue   # ReLU6 is an igemm epilogue only (the bindings reject it elsewhere)
         if cfg in BGEMM and (stem or ln or not PINGPONG):
             continue   # dense operands, plain epilogues only
         if ln and (cfg not in CGEMM or bn % 32):
@@ -350,7 +354,7 @@ def _time_concurrent(launch: Callable[[int, int], None], cands, conc: int, flush
 def tuned_config(key: Tuple, M: int, N: int, launch: Callable[[int, int], None], K: int = 64,
                  dma: bool = True, aligned64: bool = False, cgemm_only: bool = False,
                  halo: bool = False, no_split: bool = False, stem: bool = False,
-                 ln: bool = False) -> Tuple[int, int]:
+                 ln: bool = False, relu6: bool = False) -> Tuple[int, int]:
     """Pick the fastest (tile config, split-K) for ``key`` by timing each
     candidate (eager only — never during HIP-graph capture, where the
     heuristic is used).  Inside ``tuning_regime(k > 1)`` the pick is the
@@ -371,7 +375,8 @@ def tuned_config(key: Tuple, M: int, N: int, launch: Callable[[int, int], None],
             _GRAPH_TUNED.add(key)          # the leader already graph-tuned it
         return remote
     if not AUTOTUNE or torch.cuda.is_current_stream_capturing():
-        c = (UNTUNED_CGEMM_NO_SPLIT if no_split else UNTUNED_CGEMM) if cgemm_only else heuristic_config(M, N)
+        c = (UNTUNED_CGEMM_NO_SPLIT if no_split else UNTUNED_CGEMM) if cgemm_only and not relu6 \
+            else heuristic_config(M, N)
         return c, 1 if no_split else heuristic_splits(M, N, K, c)
     with _TUNE_LOCK:
         hit = _TUNED.get(key)
@@ -380,7 +385,7 @@ def tuned_config(key: Tuple, M: int, N: int, launch: Callable[[int, int], None],
         best, best_t = None, float("inf")
         times = []
         flush = _flush_buffer()
-        cands = candidates(M, N, K, dma, aligned64, cgemm_only, halo, no_split, stem, ln)
+        cands = candidates(M, N, K, dma, aligned64, cgemm_only, halo, no_split, stem, ln, relu6)
         for c, s in cands:
             try:
                 launch(c, s)   # warm (also sets the kernel's LDS attribute)

@@ -1,4 +1,4 @@
-"""Engine-level ResNet-50 timing on one GPU: HIP-graph replay of the fused
+"""Engine-level ResNet-50 / MobileNet / BERT timing on one GPU: HIP-graph replay of the fused
 program per batch bucket (no transport), plus a torch/MIOpen channels-last
 bf16 baseline of the same network for comparison."""
 import argparse
@@ -19,7 +19,7 @@ def main():
     ap.add_argument("--batch", type=int, nargs="+", default=[1, 32])
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--baseline", action="store_true")
-    ap.add_argument("--model", default="resnet50", choices=["resnet50", "resnet50-v2", "bert-base"])
+    ap.add_argument("--model", default="resnet50", choices=["resnet50", "resnet50-v2", "mobilenet-v1", "mobilenet-v2", "bert-base"])
     ap.add_argument("--graph-tune", type=int, default=1, help="whole-graph tile re-tuning at capture (0 = off)")
     args = ap.parse_args()
     import logging
@@ -33,6 +33,12 @@ def main():
         s = Servable("bert", 1, path, opts)
         r = s.runner("serving_default", ["input_ids", "input_mask", "segment_ids"], ["pooled_output", "probabilities"])
         flop_per_item = 2 * 85e6 * 128 + 4 * 12 * 128 * 128 * 768   # encoder GEMMs + attention, seq 128
+    elif args.model.startswith("mobilenet"):
+        from rust_tensorflow_serving2_amd.models import mobilenet
+        mobilenet.export(path, version=args.model.split("-")[1])
+        s = Servable("mobilenet", 1, path, opts)
+        r = s.runner("serving_default", ["input"], ["classes", "probabilities"])
+        flop_per_item = 2 * (569e6 if args.model == "mobilenet-v1" else 300e6)    # multiply-adds at 224 x 224
     else:
         resnet.export(path, version="v2" if args.model == "resnet50-v2" else "v1.5")
         s = Servable("resnet", 1, path, opts)
