@@ -52,6 +52,52 @@ def _const(g: Graph, ref) -> Optional[torch.Tensor]:
     return v if isinstance(v, torch.Tensor) else None
 
 
+def _channel_const(v: Optional[torch.Tensor], c: int, rank: int) -> Optional[torch.Tensor]:
+    """``v`` as a flat fp32 [c] vector (or a one-element tensor) when it
+    broadcasts along the LAST axis of a rank-``rank`` tensor with ``c``
+    channels and nowhere else: its shape, leading 1s dropped, is ``(c,)``, or
+    it has one element; and it has no more axes than the tensor (a longer
+    shape would raise the result's rank).  A size check alone is not enough: a
+    ``[c, 1]`` constant has ``c`` elements and scales along W, not along C."""
+    if v is None or v.dim() > rank:
+        return None
+    if v.numel() == 1:
+        return v.float().reshape(1)
+    shape = list(v.shape)
+    while shape and shape[0] == 1:
+        shape.pop(0)
+    return v.float().reshape(-1) if shape == [c] else None
+
+
+def _residual_for(res: torch.Tensor, out_shape) -> Optional[torch.Tensor]:
+    """The residual as the kernels read it (one element per output element):
+    itself, its broadcast to the output's shape, or None when adding it would
+    change the output's shape (the op then adds it with torch)."""
+    out_shape = tuple(out_shape)
+    if tuple(res.shape) == out_shape:
+        return res
+    try:
+        if tuple(torch.broadcast_shapes(tuple(res.shape), out_shape)) != out_shape:
+            return None
+    except RuntimeError:
+        return None
+    return res.expand(out_shape)
+
+
+def _add_residual_unfused(impl, ctx, node, x, res):
+    """``act(op(x) + res)`` for a residual the kernels cannot take: the op
+    without its residual, activation and post output, then torch."""
+    plain = impl.__class__.__new__(impl.__class__)
+    plain.__dict__.update(impl.__dict__)
+    plain.act, plain.post, plain.post_mode = "none", None, None
+    y = plain(ctx, node, [x])[0]
+    z = _ref_act(y.float() + res.float().to(y.device), impl.act)
+    z = z.to(y.dtype) if y.dtype == BF16 else z
+    if getattr(impl, "post", None) is None:
+        return [z.contiguous()]
+    return [o.to(y.dtype) for o in _with_post(impl, z.contiguous())]     # (the kernels' post output is bf16 too)
+
+
 class _Ctx:
     def __init__(self, g: Graph, order: List[str], fed: Set[str], fetch_refs, device, opts):
         self.g = g
@@ -202,13 +248,18 @@ class FusedConv:
             x = x.float().contiguous()            # generic: fp32 operand gather + cast in-kernel
         else:
             x = _to_bf16(x).contiguous()
-        if res is not None:
-            res = _to_bf16(res).contiguous()
         H = hip()
         n, h, w, _ = x.shape
         kh, kw = (self.khp, 8) if self.c4 else (self.kh, self.kw)
         ho = (h + pt + pb - kh) // self.sh + 1
         wo = (w + pl + pr - kw) // self.sw + 1
+        if res is not None:
+            # the kernel reads one residual element per output element: a broadcast operand
+            # ([B,1,1,C], [1,1,1,C], a scalar) is expanded first
+            res = _residual_for(res, (n, ho, wo, self.cout))
+            if res is None:
+                return _add_residual_unfused(self, ctx, node, ins[0], O.to_torch(ins[1]))
+            res = _to_bf16(res).contiguous()
         M = n * ho * wo
         args = (x, self.w, self.b, res, kh, kw, self.sh, self.sw, pt, pb, pl, pr, ACT[self.act])
         out = torch.empty((n, ho, wo, self.cout), device=x.device, dtype=BF16)
@@ -331,6 +382,13 @@ class FusedDualConv:
             return _with_post(self, _ref_act(y, self.act).contiguous())
         from ..ops import ACT, hip, tuned_config
         H = hip()
+        xs = x[:, ::self.sh, ::self.sw, :]
+        if h.dim() != 4 or tuple(xs.shape[:3]) != tuple(h.shape[:3]):
+            # the two convs' outputs only broadcast against each other (a [B,1,1,C] projection): the
+            # kernel reads both sources at every output pixel, so the sum is taken with torch
+            w = self.w.float()
+            y = h.float() @ w[:, :self.c1].t() + xs.float() @ w[:, self.c1:self.c1 + self.c2].t() + self.b
+            return [o.to(BF16) for o in _with_post(self, _ref_act(y, self.act).contiguous())]
         h, x = _to_bf16(h).contiguous(), _to_bf16(x).contiguous()
         n, ho, wo, _ = h.shape
         out = torch.empty((n, ho, wo, self.cout), device=h.device, dtype=BF16)
@@ -388,6 +446,11 @@ class FusedMatMul:
         from ..ops import ACT, hip, tuned_config
         H = hip()
         x = _to_bf16(x)
+        if res is not None:
+            # one residual element per output element: a [1, N] or [N] operand is expanded first
+            res = _residual_for(res, list(x.shape[:-1]) + [self.n])
+            if res is None:
+                return _add_residual_unfused(self, ctx, node, ins[0], O.to_torch(ins[1]))
         if not (x.dim() == 2 and x.stride(1) == 1 and x.stride(0) % 8 == 0 and res is None):
             # (a row-strided 2-D view -- BERT's pooler reading each sequence's
             # first token out of [B, S, H] -- is read in place: no copy kernel)
@@ -637,7 +700,8 @@ class MatMulLN:
             return ln(ctx, node, mm(ctx, node, ins))
         x = O.to_torch(ins[0])
         res = O.to_torch(ins[1]) if len(ins) > 1 else None
-        if not (self.use_hip and x.is_cuda and x.shape[-1] == mm.k and (res is None or res.shape[-1] == mm.n)):
+        if not (self.use_hip and x.is_cuda and x.shape[-1] == mm.k and
+                (res is None or tuple(res.shape) == tuple(x.shape[:-1]) + (mm.n,))):
             return split()
         from ..ops import hip, tuned_choice
         H = hip()
@@ -784,12 +848,20 @@ for _op in ("_FusedConv2D", "_FusedDepthwiseConv2D", "_FusedDualConv", "_FusedMa
 
 
 class GlobalAvgPool:
-    def __init__(self, keep_dims: bool, use_hip: bool):
+    """``Mean`` over the axes the pass saw ({1, 2} or {-3, -2}).  Whether those
+    are H and W of an NHWC tensor depends on the rank, which only the call
+    knows: any other rank gets the Mean's own semantics from torch."""
+
+    def __init__(self, keep_dims: bool, use_hip: bool, axes=(1, 2)):
         self.keep = keep_dims
         self.use_hip = use_hip
+        self.axes = tuple(int(a) for a in axes)
 
     def __call__(self, ctx, node, ins):
         x = O.to_torch(ins[0])
+        if x.dim() != 4 or sorted(a % 4 for a in self.axes) != [1, 2]:
+            axes = sorted({a % x.dim() for a in self.axes})
+            return [x.float().mean(dim=axes, keepdim=self.keep)]
         if self.use_hip and x.is_cuda and x.shape[-1] % 8 == 0:
             from ..ops import hip
             y = hip().global_avgpool(_to_bf16(x).contiguous())
@@ -799,13 +871,16 @@ class GlobalAvgPool:
 
 
 class MaxPool:
-    def __init__(self, ksize, strides, padding, use_hip):
+    def __init__(self, ksize, strides, padding, use_hip, pads=(0, 0, 0, 0)):
         self.kh, self.kw = ksize
         self.sh, self.sw = strides
-        self.padding = padding
+        self.padding = padding          # "SAME" | "VALID" | "EXPLICIT"
+        self.pads = tuple(pads)         # (pt, pb, pl, pr) for EXPLICIT
         self.use_hip = use_hip
         self.post = None
         self.post_mode = None
+
+    pads_for = FusedConv.pads_for
 
     def set_post(self, scale, shift, act, mode, device=None):
         # on the device up front: a host->device copy inside HIP-graph capture is illegal
@@ -818,11 +893,7 @@ class MaxPool:
 
     def __call__(self, ctx, node, ins):
         x = O.to_torch(ins[0])
-        h, w = x.shape[1], x.shape[2]
-        if self.padding == "SAME":
-            (pt, pb), (pl, pr) = O.tf_same_pads(h, self.kh, self.sh), O.tf_same_pads(w, self.kw, self.sw)
-        else:
-            pt = pb = pl = pr = 0
+        pt, pb, pl, pr = self.pads_for(x.shape[1], x.shape[2])
         if self.use_hip and x.is_cuda and x.shape[-1] % 8 == 0 and self.post_mode != "dual":
             from ..ops import ACT, hip
             kw = {}
@@ -837,13 +908,21 @@ class MaxPool:
 
 
 class SoftmaxArgMax:
-    def __init__(self, use_hip, classes_dtype):
+    """``Softmax(x)`` and ``ArgMax(x, axis)`` of the same x.  The pass sees the
+    axis (1 or -1) but not the rank: where the axis is not the last one (axis 1
+    of a rank-3 tensor) the classes come from torch, over that axis."""
+
+    def __init__(self, use_hip, classes_dtype, axis=-1):
         self.use_hip = use_hip
         self.cdt = classes_dtype
+        self.axis = int(axis)
 
     def __call__(self, ctx, node, ins):
         x = O.to_torch(ins[0])
-        if self.use_hip and x.is_cuda and x.dim() == 2 and x.dtype in (torch.float32, BF16):
+        if x.dim() and self.axis % x.dim() != x.dim() - 1:
+            probs = torch.softmax(x.float(), dim=-1)
+            cls = torch.argmax(x.float(), dim=self.axis)
+        elif self.use_hip and x.is_cuda and x.dim() == 2 and x.dtype in (torch.float32, BF16):
             from ..ops import hip
             if x.stride(-1) != 1:
                 x = x.contiguous()
@@ -860,8 +939,9 @@ class ClassifierHead:
     dot products, then bias + partial sums + softmax/argmax) instead of three
     with a 16-workgroup, 2048-deep serial GEMM in the middle."""
 
-    def __init__(self, mm: FusedMatMul, classes_dtype, use_hip: bool):
-        self.n = mm.n
+    def __init__(self, mm: FusedMatMul, classes_dtype, use_hip: bool, axes=(1, 2)):
+        self.n, self.k = mm.n, mm.k
+        self.axes = tuple(int(a) for a in axes)     # the Mean's own axes: H, W only at rank 4
         self.cdt = classes_dtype
         self.use_hip = use_hip and mm.use_hip and mm.k in (512, 1024, 2048, 4096)
         if mm.use_hip:
@@ -871,7 +951,8 @@ class ClassifierHead:
 
     def __call__(self, ctx, node, ins):
         x = O.to_torch(ins[0])
-        if self.use_hip and x.is_cuda and x.dim() == 4 and x.shape[-1] == self.w.shape[1]:
+        nhwc = x.dim() == 4 and sorted(a % 4 for a in self.axes) == [1, 2]
+        if self.use_hip and x.is_cuda and nhwc and x.shape[-1] == self.w.shape[1]:
             from ..ops import current_head_host_rows, hip
             rows = current_head_host_rows()
             if rows is not None:
@@ -886,7 +967,8 @@ class ClassifierHead:
                 return [probs, cls]
             probs, cls = hip().classifier_head(_to_bf16(x).contiguous(), self.w, self.b, self.n)
         else:
-            pooled = x.float().mean(dim=(1, 2))
+            # (the Squeeze / Reshape between the pool and the GEMM gave it [rows, K] in row-major order)
+            pooled = x.float().mean(dim=sorted({a % x.dim() for a in self.axes})).reshape(-1, self.k)
             if hasattr(self, "w_ref"):
                 logits = pooled @ self.w_ref.to(x.device) + self.b_ref.to(x.device)
             else:
@@ -925,10 +1007,7 @@ class StemPool:
         pt, pb, pl, pr = conv.pads_for(x.shape[1], x.shape[2])
         hc = (x.shape[1] + pt + pb - conv.kh) // conv.sh + 1
         wc = (x.shape[2] + pl + pr - conv.kw) // conv.sw + 1
-        if pool.padding == "SAME":
-            (ppt, ppb), (ppl, ppr) = O.tf_same_pads(hc, 3, 2), O.tf_same_pads(wc, 3, 2)
-        else:
-            ppt = ppb = ppl = ppr = 0
+        ppt, ppb, ppl, ppr = pool.pads_for(hc, wc)
         kw = {}
         if pool.post is not None:
             sc, sh, act = pool.post
@@ -995,8 +1074,9 @@ class ChainConv:
         if self.dual:
             return self._call_dual(x, O.to_torch(ins[1]), split)
         res = O.to_torch(ins[1]) if len(ins) > 1 else None
-        if not (self.use_hip and x.is_cuda and x.dim() == 4 and x.shape[-1] == a.cin):
-            return split()
+        if not (self.use_hip and x.is_cuda and x.dim() == 4 and x.shape[-1] == a.cin) or \
+                (res is not None and tuple(res.shape) != tuple(x.shape[:3]) + (a.cout,)):
+            return split()              # (a broadcast residual: the conv op expands it)
         from ..ops import ACT, hip, tuned_choice
         xb = _to_bf16(x).contiguous()
         rb = None if res is None else _to_bf16(res).contiguous()
@@ -1057,6 +1137,15 @@ def fuse_classifier_head(g, order, fed, fetch_refs, device, opts):
             n = g.nodes.get(ref[0])
         return ref, n
 
+    def keeps_rows(nodes, cols) -> bool:
+        """No Squeeze, and every Reshape is to [rows, cols]: the op in between sees the same rows."""
+        for p in nodes:
+            shp = _const(g, p.inputs[1]) if p.op == "Reshape" else None
+            if p.op == "Squeeze" or (p.op == "Reshape" and
+                                     (shp is None or shp.numel() != 2 or int(shp.reshape(-1)[1]) != cols)):
+                return False
+        return True
+
     for name in order:
         sm = g.nodes.get(name)
         if sm is None or sm.op != "_SoftmaxArgMax" or not sm.inputs:
@@ -1066,15 +1155,21 @@ def fuse_classifier_head(g, order, fed, fetch_refs, device, opts):
         if mm is None or mm.op != "_FusedMatMul" or ref[1] != 0 or len(mm.inputs) != 1 or not single(mm):
             continue
         impl = mm.attrs["_impl"]
+        sm_impl = sm.attrs["_impl"]
         if impl.act != "none":
             continue
+        if not keeps_rows(chain, impl.n):
+            continue                  # the logits are regrouped before the softmax
         chain.append(mm)
+        before = len(chain)
         ref, gap = walk(mm.inputs[0], chain)
         if gap is None or gap.op != "_GlobalAvgPool" or ref[1] != 0 or not single(gap):
             continue
+        if not all(p.op != "Reshape" or keeps_rows([p], impl.k) for p in chain[before:]):
+            continue
+        gap_impl = gap.attrs["_impl"]
         chain.append(gap)
-        sm_impl = sm.attrs["_impl"]
-        head = ClassifierHead(impl, sm_impl.cdt, c.use_hip)
+        head = ClassifierHead(impl, sm_impl.cdt, c.use_hip, gap_impl.axes)
         sm.op = "_ClassifierHead"
         sm.inputs = [gap.inputs[0]]
         sm.attrs = {"_impl": head}
@@ -1097,7 +1192,8 @@ def fuse_stem_pool(g, order, fed, fetch_refs, device, opts):
         if p is None or p.op != "_MaxPool" or not p.inputs or p.inputs[0][1] != 0:
             continue
         pool = p.attrs["_impl"]
-        if (pool.kh, pool.kw, pool.sh, pool.sw) != (3, 3, 2, 2) or pool.post_mode == "dual":
+        if (pool.kh, pool.kw, pool.sh, pool.sw) != (3, 3, 2, 2) or pool.post_mode == "dual" or \
+                pool.padding not in ("SAME", "VALID"):
             continue
         cn = g.nodes.get(p.inputs[0][0])
         if cn is None or cn.op != "_FusedConv2D" or len(cn.inputs) != 1 or c.only_consumer(cn.name) is not p:
@@ -1144,7 +1240,7 @@ def fuse_conv(g, order, fed, fetch_refs, device, opts):
             pv = _const(g, prod.inputs[1])
             if pv is not None:
                 p = [int(v) for v in pv.reshape(-1).tolist()]
-                if p[0] == p[1] == p[6] == p[7] == 0 and min(p) >= 0:
+                if len(p) == 8 and p[0] == p[1] == p[6] == p[7] == 0 and min(p) >= 0:
                     chain.append(prod)
                     x_ref = prod.inputs[0]
                     padding, pads = "EXPLICIT", (p[2], p[3], p[4], p[5])
@@ -1159,7 +1255,7 @@ def fuse_conv(g, order, fed, fetch_refs, device, opts):
         nxt = c.only_consumer(cur.name)
         if nxt is not None and nxt.op == "BiasAdd" and nxt.inputs[0] == (cur.name, 0):
             b = _const(g, nxt.inputs[1])
-            if b is not None and b.numel() == cout:
+            if b is not None and tuple(b.shape) == (cout,):
                 bias = bias + b.float()
                 chain.append(nxt)
                 cur = nxt
@@ -1181,9 +1277,9 @@ def fuse_conv(g, order, fed, fetch_refs, device, opts):
         # folded into the weights and bias
         if nxt is not None and nxt.op == "Mul" and len(nxt.inputs) == 2 and (cur.name, 0) in nxt.inputs:
             other = nxt.inputs[1] if nxt.inputs[0] == (cur.name, 0) else nxt.inputs[0]
-            sv = _const(g, other)
-            if sv is not None and sv.numel() in (1, cout) and other != (cur.name, 0):
-                sv = sv.float().reshape(-1)
+            # by shape, not by size: [C], [1,1,1,C] or one element (a [C,1] constant scales along W)
+            sv = _channel_const(_const(g, other), cout, 4)
+            if sv is not None and other != (cur.name, 0):
                 w = w * sv
                 bias = bias * sv
                 chain.append(nxt)
@@ -1242,7 +1338,7 @@ def fuse_depthwise(g, order, fed, fetch_refs, device, opts):
             pv = _const(g, prod.inputs[1])
             if pv is not None:
                 p = [int(v) for v in pv.reshape(-1).tolist()]
-                if p[0] == p[1] == p[6] == p[7] == 0 and min(p) >= 0:
+                if len(p) == 8 and p[0] == p[1] == p[6] == p[7] == 0 and min(p) >= 0:
                     chain.append(prod)
                     x_ref = prod.inputs[0]
                     padding, pads = "EXPLICIT", (p[2], p[3], p[4], p[5])
@@ -1255,7 +1351,7 @@ def fuse_depthwise(g, order, fed, fetch_refs, device, opts):
         nxt = c.only_consumer(cur.name)
         if nxt is not None and nxt.op == "BiasAdd" and nxt.inputs[0] == (cur.name, 0):
             b = _const(g, nxt.inputs[1])
-            if b is not None and b.numel() == ch:
+            if b is not None and tuple(b.shape) == (ch,):
                 bias = bias + b.float()
                 chain.append(nxt)
                 cur = nxt
@@ -1315,9 +1411,10 @@ def fuse_matmul(g, order, fed, fetch_refs, device, opts):
         act = "none"
         nxt = c.only_consumer(cur.name)
         if nxt is not None and nxt.op in ("BiasAdd", "Add", "AddV2") and nxt.inputs[0] == (cur.name, 0):
-            b = _const(g, nxt.inputs[1])
-            if b is not None and b.numel() == ndim:
-                bias = b.float().reshape(-1)
+            # by shape, not by size: [N], [1,N] or one element (an [N,1] constant adds a column)
+            b = _channel_const(_const(g, nxt.inputs[1]), ndim, 1 if nxt.op == "BiasAdd" else 2)
+            if b is not None:
+                bias = b.expand(ndim).contiguous()
                 chain.append(nxt)
                 cur = nxt
                 nxt = c.only_consumer(cur.name)
@@ -1362,14 +1459,26 @@ def fuse_pools(g, order, fed, fetch_refs, device, opts):
             continue
         if n.op == "Mean":
             ax = _const(g, n.inputs[1])
-            if ax is not None and sorted(int(a) for a in ax.reshape(-1).tolist()) in ([1, 2], [-3, -2]):
+            axes = None if ax is None else [int(a) for a in ax.reshape(-1).tolist()]
+            if axes is not None and sorted(axes) in ([1, 2], [-3, -2]):
+                # (H and W of an NHWC tensor if its rank is 4: the op checks, and keeps the axes for any other rank)
                 n.op = "_GlobalAvgPool"
-                n.attrs = {"_impl": GlobalAvgPool(bool(n.attr("keep_dims", False)), c.use_hip)}
+                n.attrs = {"_impl": GlobalAvgPool(bool(n.attr("keep_dims", False)), c.use_hip, axes)}
                 n.inputs = [n.inputs[0]]
         elif n.op == "MaxPool" and n.sattr("data_format", "NHWC") == "NHWC":
             k, s = n.attr("ksize"), n.attr("strides")
+            padding, pads = n.sattr("padding", "VALID"), (0, 0, 0, 0)
+            if not (k[0] == k[3] == s[0] == s[3] == 1) or padding not in ("SAME", "VALID", "EXPLICIT"):
+                continue
+            if padding == "EXPLICIT":
+                ep = list(n.attr("explicit_paddings", []) or [])
+                if len(ep) != 8 or ep[0] or ep[1] or ep[6] or ep[7] or min(ep) < 0:
+                    continue
+                pads = (ep[2], ep[3], ep[4], ep[5])
+                if max(pads[0], pads[1]) >= k[1] or max(pads[2], pads[3]) >= k[2]:
+                    continue          # a window could lie wholly in the padding
             n.op = "_MaxPool"
-            n.attrs = {"_impl": MaxPool((k[1], k[2]), (s[1], s[2]), n.sattr("padding", "VALID"), c.use_hip)}
+            n.attrs = {"_impl": MaxPool((k[1], k[2]), (s[1], s[2]), padding, c.use_hip, pads)}
 
 
 def fuse_softmax_argmax(g, order, fed, fetch_refs, device, opts):
@@ -1390,7 +1499,7 @@ def fuse_softmax_argmax(g, order, fed, fetch_refs, device, opts):
             sm, am = d["sm"], d["am"]
             cdt = O.DT_TO_TORCH.get(am.attrs.get("output_type", T.DT_INT64), torch.int64)
             sm.op = "_SoftmaxArgMax"
-            sm.attrs = {"_impl": SoftmaxArgMax(c.use_hip, cdt)}
+            sm.attrs = {"_impl": SoftmaxArgMax(c.use_hip, cdt, int(_const(g, am.inputs[1]).reshape(-1)[0]))}
             am.op = "Identity"
             am.inputs = [(sm.name, 1)]
             am.attrs = {}

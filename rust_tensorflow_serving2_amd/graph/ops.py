@@ -107,6 +107,15 @@ def _same_device(a: torch.Tensor, b: torch.Tensor):
     return a, b
 
 
+def _same_float(a: torch.Tensor, b: torch.Tensor):
+    """A bf16 activation from a fused op against an fp32 tensor: torch.matmul
+    does not promote, the elementwise ops do -- to fp32, as here."""
+    if a.dtype != b.dtype and a.is_floating_point() and b.is_floating_point():
+        dt = torch.promote_types(a.dtype, b.dtype)
+        a, b = a.to(dt), b.to(dt)
+    return a, b
+
+
 # ------------------------------------------------------------------ leaves
 @op("Const")
 def _const(ctx, n, ins):
@@ -558,7 +567,7 @@ def _topk(ctx, n, ins):
 # ------------------------------------------------------------------ linear algebra
 @op("MatMul")
 def _matmul(ctx, n, ins):
-    a, b = _same_device(to_torch(ins[0]), to_torch(ins[1]))
+    a, b = _same_float(*_same_device(to_torch(ins[0]), to_torch(ins[1])))
     if n.attr("transpose_a", False):
         a = a.t()
     if n.attr("transpose_b", False):
@@ -568,7 +577,7 @@ def _matmul(ctx, n, ins):
 
 @op("BatchMatMul", "BatchMatMulV2", "BatchMatMulV3")
 def _bmm(ctx, n, ins):
-    a, b = _same_device(to_torch(ins[0]), to_torch(ins[1]))
+    a, b = _same_float(*_same_device(to_torch(ins[0]), to_torch(ins[1])))
     if n.attr("adj_x", False):
         a = a.transpose(-1, -2)
     if n.attr("adj_y", False):

@@ -94,21 +94,47 @@ def _axes_last(g, ref, rank_hint=None) -> bool:
     return a == -1 or (rank_hint is not None and a == rank_hint - 1)
 
 
+def _last_axis_const(v: torch.Tensor) -> Optional[torch.Tensor]:
+    """``v`` flattened when it varies along its last axis only (shape, leading
+    1s dropped, is ``(cols,)``, or it has one element), else None."""
+    if v.numel() == 1:
+        return v.reshape(1)
+    shape = list(v.shape)
+    while shape and shape[0] == 1:
+        shape.pop(0)
+    return v.reshape(-1) if len(shape) == 1 else None
+
+
 # ------------------------------------------------------------------ fused impls
 class LayerNormOp:
     def __init__(self, gamma, beta, eps, device, use_hip):
         self.eps = float(eps)
         self.use_hip = use_hip
+        # [cols] vectors, or one element each (a scalar gamma / beta: expanded
+        # to the row length, which only the call knows)
         self.g = to_device(gamma.float().reshape(-1), device)
         self.b = to_device(beta.float().reshape(-1), device)
 
+        self._rows = None             # (cols, gamma [cols], beta [cols]) of a scalar gamma / beta, cached
+
+    def params(self, cols: int):
+        """(gamma, beta) as [cols] vectors; the op's own weights stay as they were bound."""
+        if self.g.numel() == self.b.numel() and self.g.numel() != 1:
+            return self.g, self.b
+        if self._rows is None or self._rows[0] != cols:
+            g = self.g.expand(cols).contiguous() if self.g.numel() == 1 else self.g
+            b = self.b.expand(cols).contiguous() if self.b.numel() == 1 else self.b
+            self._rows = (cols, g, b)
+        return self._rows[1], self._rows[2]
+
     def __call__(self, ctx, node, ins):
         x = O.to_torch(ins[0])
-        if self.use_hip and x.is_cuda and x.shape[-1] % 8 == 0 and x.shape[-1] == self.g.numel():
+        g, b = self.params(x.shape[-1])
+        if self.use_hip and x.is_cuda and x.shape[-1] % 8 == 0 and x.shape[-1] == g.numel():
             from ..ops import hip
             from .fused import _to_bf16
-            return [hip().layernorm(_to_bf16(x).contiguous(), None, self.g, self.b, self.eps)]
-        y = F.layer_norm(x.float(), (x.shape[-1],), self.g.to(x.device), self.b.to(x.device), self.eps)
+            return [hip().layernorm(_to_bf16(x).contiguous(), None, g, b, self.eps)]
+        y = F.layer_norm(x.float(), (x.shape[-1],), g.to(x.device), b.to(x.device), self.eps)
         return [y if not x.is_cuda else y.to(x.dtype)]
 
 
@@ -303,7 +329,14 @@ def _match_ln(g, c, out: Node):
                 continue
             if not _interior_ok(c, interior, out):
                 continue
-            return x_ref, gamma, beta, eps, interior
+            # the statistics broadcast against x only with keep_dims; gamma and beta must scale along the
+            # last axis alone: a vector, [1, ..., cols], or one element (a [S, 1] constant is per row)
+            if not (mean.attr("keep_dims", False) and var.attr("keep_dims", False)):
+                continue
+            gv, bv = _last_axis_const(gamma), _last_axis_const(beta)
+            if gv is None or bv is None or (gv.numel() != bv.numel() and 1 not in (gv.numel(), bv.numel())):
+                continue
+            return x_ref, gv, bv, eps, interior
     return None
 
 
@@ -315,9 +348,10 @@ def _dense_src(g, c, ref):
     bias = None
     if n is not None and n.op in ("BiasAdd", "Add", "AddV2"):
         b = _const_t(g, n.inputs[1])
-        if b is None:
+        # by shape, not by size: [N], [1, N] or one element (an [M, 1] constant adds a column)
+        bias = None if b is None or b.dim() > 2 else _last_axis_const(b.float())
+        if bias is None:
             return None
-        bias = b.float().reshape(-1)
         nodes.append(n)
         n = _node(g, n.inputs[0])
     if n is None or n.op != "MatMul" or n.attr("transpose_a", False):
@@ -331,6 +365,10 @@ def _dense_src(g, c, ref):
     nodes.append(n)
     if bias is None:
         bias = torch.zeros(w.shape[1], device=w.device)
+    elif bias.numel() == 1:
+        bias = bias.expand(w.shape[1]).contiguous()
+    elif bias.numel() != w.shape[1]:
+        return None
     return n.inputs[0], w, bias, nodes
 
 
@@ -410,8 +448,8 @@ def fuse_attention(g, order, fed, fetch_refs, device, opts):
         if (hk[1], hk[2], hk[3]) != (S, H, D) or (hv[1], hv[2], hv[3]) != (S, H, D):
             continue
         fshape = _const_t(g, out.inputs[1])
-        if fshape is None or fshape.reshape(-1).tolist()[-1] != H * D:
-            continue
+        if fshape is None or fshape.numel() != 2 or fshape.reshape(-1).tolist()[-1] != H * D:
+            continue                  # (the op returns [B * S, H * D])
         dq, dk, dv = _dense_src(g, c, hq[0]), _dense_src(g, c, hk[0]), _dense_src(g, c, hv[0])
         interior += hq[4] + hk[4] + hv[4]
         if dq and dk and dv and dq[0] == dk[0] == dv[0]:
@@ -544,6 +582,9 @@ def fuse_embedding(g, order, fed, fetch_refs, device, opts):
             if p is not None and tuple(p.shape) not in ((1, S, Hd), (S, Hd)):
                 continue
             impl = ln.attrs["_impl"]
+            if impl.g.numel() not in (1, Hd) or impl.b.numel() not in (1, Hd):
+                continue
+            ln_g, ln_b = impl.params(Hd)
             nodes = interior + [n for gt in gathers for n in gt[3]]
             if not _interior_ok(c, nodes, ln):
                 continue
@@ -552,7 +593,7 @@ def fuse_embedding(g, order, fed, fetch_refs, device, opts):
             ln.op = "_EmbeddingLN"
             ln.inputs = [gt[1] for gt in gathers]
             ln.ctrl = []
-            ln.attrs = {"_impl": EmbeddingLNOp([gt[0] for gt in gathers], p, S, impl.g, impl.b, impl.eps,
+            ln.attrs = {"_impl": EmbeddingLNOp([gt[0] for gt in gathers], p, S, ln_g, ln_b, impl.eps,
                                                device, c.use_hip)}
             c.refresh()
 

@@ -74,9 +74,9 @@ class Picks:
         self.choice = None
 
     def tuned_config(self, key, M, N, launch, K=64, dma=True, aligned64=False, cgemm_only=False, halo=False,
-                     no_split=False, stem=False, ln=False):
+                     no_split=False, stem=False, ln=False, relu6=False):
         flags = dict(dma=dma, aligned64=aligned64, cgemm_only=cgemm_only, halo=halo, no_split=no_split, stem=stem,
-                     ln=ln)
+                     ln=ln, relu6=relu6)
         offered = REAL_TUNED_CONFIG(key, M, N, _never, K, **flags)
         self.calls.append(dict(key=key, M=M, N=N, K=K, flags=flags, offered=offered))
         return self.force if self.force is not None else offered
