@@ -9,7 +9,13 @@ a single consumer and is not fetched):
   explicit padding, residual add + ReLU in the MFMA kernel's epilogue.  A conv
   whose input has C % 8 != 0 (the RGB stem) reads the fp32 request tensor
   directly (ingest cast fused into the operand loads).
-* ``[Pad] -> DepthwiseConv2dNative -> [BiasAdd] -> [FusedBatchNorm*] -> [Relu|Relu6]``
+* ``Mul(Relu6(Add(x, 3)), 1/6)`` => ``_HardSigmoid(x)``; ``Mul(x, _HardSigmoid(x))`` (or
+  the slim association ``Mul(Mul(x, Relu6(Add(x, 3))), 1/6)``) => ``_HardSwish(x)``, which
+  ``_FusedConv2D`` / ``_FusedDepthwiseConv2D`` take as their closing activation
+  (MobileNetV3; igemm and dwconv epilogues).
+* ``Mul(x, _HardSigmoid(Conv2D 1x1(act(Conv2D 1x1(_GlobalAvgPool(x))))))`` =>
+  ``_SqueezeExcite(x)``: fp32 FC weights, ``se_gate`` + ``se_scale`` (kernels/se.hip).
+* ``[Pad] -> DepthwiseConv2dNative -> [BiasAdd] -> [FusedBatchNorm*] -> [Relu|Relu6|_HardSwish]``
   => ``_FusedDepthwiseConv2D`` (channel multiplier 1): BN folded into the fp32
   filter, one ``dwconv2d`` launch (kernels/dwconv.hip).  ``Relu6`` also fuses
   into ``_FusedConv2D`` (MobileNet's pointwise convs).
@@ -41,6 +47,9 @@ from .ir import Graph, Node
 from .placement import to_device, zeros
 
 BF16 = torch.bfloat16
+IGEMM_ONLY_ACTS = ("relu6", "hard_swish")       # ops.IGEMM_ONLY_ACTS: no cgemm / bgemm / halo epilogue
+# the ops fuse_conv / fuse_depthwise take as the closing activation -> the kernels' name for it
+_CLOSING_ACTS = {"Relu": "relu", "Relu6": "relu6", "_HardSwish": "hard_swish"}
 
 
 # ------------------------------------------------------------------ helpers
@@ -214,7 +223,8 @@ class FusedConv:
         """The fused kernels write the post output only on the cgemm / halo
         paths (64-aligned channels); the CPU reference always can."""
         return not self.use_hip or (not self.c4 and self.cin % 64 == 0 and self.cout % 8 == 0 and
-                                    self.act != "relu6")      # (the post output is cgemm / halo only; they have no relu6)
+                                    self.act not in IGEMM_ONLY_ACTS)   # (the post output is cgemm / halo only; they
+        #                                                                  have no relu6 / hard_swish)
 
     def pads_for(self, h, w):
         if self.padding == "SAME":
@@ -279,8 +289,8 @@ class FusedConv:
             (("nohalo",) if halo_shape and self.sw == 1 and not halo else ())
         kw_post, outs = _post_kwargs(self, out)
         run = lambda c, s: H.conv2d(*args, cfg=c, out=out, splits=s, **kw_post)  # noqa
-        # (ReLU6 is an igemm epilogue only: those launches tune over the igemm configs)
-        flags = {"relu6": True} if self.act == "relu6" else {}
+        # (ReLU6 and hard-swish are igemm epilogues only: those launches tune over the igemm configs)
+        flags = {"relu6": True} if self.act in IGEMM_ONLY_ACTS else {}
         cfg, splits = tuned_config(key, M, self.cout, run, K, dma, aligned, halo=halo,
                                    cgemm_only=self.post is not None, stem=self.c4, **flags)
         run(cfg, splits)
@@ -828,6 +838,10 @@ def _ref_act(y, act):
         return torch.relu(y)
     if act == "relu6":
         return torch.clamp(y, 0.0, 6.0)
+    if act == "hard_sigmoid":
+        return torch.clamp(y + 3.0, 0.0, 6.0) * (1.0 / 6.0)
+    if act == "hard_swish":
+        return y * (torch.clamp(y + 3.0, 0.0, 6.0) * (1.0 / 6.0))
     if act == "tanh":
         return torch.tanh(y)
     if act == "gelu_tanh":
@@ -842,6 +856,7 @@ def _impl_op(ctx, node, ins):
 
 
 for _op in ("_FusedConv2D", "_FusedDepthwiseConv2D", "_FusedDualConv", "_FusedMatMul", "_GlobalAvgPool", "_MaxPool",
+            "_SqueezeExcite",
             "_SoftmaxArgMax", "_LayerNorm",
             "_FusedQKV", "_Attention", "_EmbeddingLN", "_KeyMaskAdder", "_DenseSoftmax"):
     O.OPS[_op] = _impl_op
@@ -1292,8 +1307,8 @@ def fuse_conv(g, order, fed, fetch_refs, device, opts):
                 chain.append(nxt)
                 cur = nxt
                 nxt = c.only_consumer(cur.name)
-        if nxt is not None and nxt.op in ("Relu", "Relu6"):
-            act = nxt.op.lower()
+        if nxt is not None and nxt.op in _CLOSING_ACTS:
+            act = _CLOSING_ACTS[nxt.op]
             chain.append(nxt)
             cur = nxt
         impl = FusedConv(w, bias, (strides[1], strides[2]), padding, pads, act, device, c.use_hip, cur.name)
@@ -1303,7 +1318,7 @@ def fuse_conv(g, order, fed, fetch_refs, device, opts):
 
 
 def fuse_depthwise(g, order, fed, fetch_refs, device, opts):
-    """``[Pad ->] DepthwiseConv2dNative [-> BiasAdd] [-> FusedBatchNorm*] [-> Relu | Relu6]``
+    """``[Pad ->] DepthwiseConv2dNative [-> BiasAdd] [-> FusedBatchNorm*] [-> Relu | Relu6 | _HardSwish]``
     -> ``_FusedDepthwiseConv2D``, under fuse_conv's guards (NHWC, dilation 1, a
     constant 4-D filter, an inference BatchNorm whose only used output is y, no
     fetch inside the chain, single consumers) and channel multiplier 1.  On the
@@ -1365,13 +1380,285 @@ def fuse_depthwise(g, order, fed, fetch_refs, device, opts):
                 chain.append(nxt)
                 cur = nxt
                 nxt = c.only_consumer(cur.name)
-        if nxt is not None and nxt.op in ("Relu", "Relu6"):
-            act = nxt.op.lower()
+        if nxt is not None and nxt.op in _CLOSING_ACTS:
+            act = _CLOSING_ACTS[nxt.op]
             chain.append(nxt)
             cur = nxt
         impl = FusedDepthwiseConv(w, bias, (strides[1], strides[2]), padding, pads, act, device, c.use_hip, cur.name)
         _finalize(g, chain, "_FusedDepthwiseConv2D", [x_ref], {"_impl": impl})
         c.refresh()
+
+
+# ------------------------------------------------------------------ hard activations (MobileNetV3)
+def _hard_sigmoid_op(ctx, node, ins):
+    """clamp(x + 3, 0, 6) * c with the graph's own c (1/6 within 1e-4), in the
+    order the unfused nodes computed it."""
+    x = O.to_torch(ins[0])
+    y = torch.clamp(x.float() + 3.0, 0.0, 6.0) * float(node.attr("scale", 1.0 / 6.0))
+    return [y.to(x.dtype) if x.dtype == BF16 else y]
+
+
+def _hard_swish_op(ctx, node, ins):
+    x = O.to_torch(ins[0])
+    xf = x.float()
+    y = xf * (torch.clamp(xf + 3.0, 0.0, 6.0) * float(node.attr("scale", 1.0 / 6.0)))
+    return [y.to(x.dtype) if x.dtype == BF16 else y]
+
+
+O.OPS["_HardSigmoid"] = _hard_sigmoid_op
+O.OPS["_HardSwish"] = _hard_swish_op
+
+
+def _one_element(g: Graph, ref, want: float, rel: float) -> Optional[float]:
+    """The value of a one-element floating constant (a scalar or a [1]: by
+    shape, a [C] constant of equal entries is not one) within ``rel`` of
+    ``want``, else None."""
+    v = _const(g, ref)
+    if v is None or v.numel() != 1 or v.dim() > 1 or not v.is_floating_point():
+        return None
+    f = float(v.reshape(-1)[0])
+    return f if abs(f - want) <= rel * abs(want) else None
+
+
+def _other(node: Node, ref):
+    """The other input of a two-input node one of whose inputs is ``ref``."""
+    if len(node.inputs) != 2 or ref not in node.inputs:
+        return None
+    return node.inputs[1] if node.inputs[0] == ref else node.inputs[0]
+
+
+def _relu6_of_x_plus_3(g: Graph, c: _Ctx, ref, reader: Node):
+    """``ref`` = Relu6(Add|AddV2(x, 3)) read by ``reader`` alone -> (x, [add, relu6]) or None."""
+    r = g.nodes.get(ref[0])
+    if r is None or ref[1] != 0 or r.op != "Relu6" or len(r.inputs) != 1 or c.only_consumer(r.name) is not reader:
+        return None
+    a = g.nodes.get(r.inputs[0][0])
+    if a is None or r.inputs[0][1] != 0 or a.op not in ("Add", "AddV2") or len(a.inputs) != 2 or \
+            c.only_consumer(a.name) is not r:
+        return None
+    for x_ref, k_ref in ((a.inputs[0], a.inputs[1]), (a.inputs[1], a.inputs[0])):
+        if _one_element(g, k_ref, 3.0, 1e-6) is not None and _const(g, x_ref) is None:
+            return x_ref, [a, r]
+    return None
+
+
+HARD_SCALE_REL = 1e-4       # slim writes 0.16667 for 1/6 (2e-5 off); docs/numerics.md
+
+
+def fuse_hard_activations(g, order, fed, fetch_refs, device, opts):
+    """``Mul(Relu6(Add|AddV2(x, 3)), c)`` -> ``_HardSigmoid(x)``;
+    ``Mul(x, _HardSigmoid(x))`` and the slim association ``Mul(Mul(x,
+    Relu6(Add(x, 3))), c)`` -> ``_HardSwish(x)``.  Operands in either order; 3
+    and c one-element constants, c within 1e-4 of 1/6 (kept on the node: the
+    standalone op multiplies by it); inner nodes read once and not fetched;
+    x may have other readers."""
+    c = _Ctx(g, order, fed, fetch_refs, device, opts)
+    for name in order:
+        m = g.nodes.get(name)
+        if m is None or m.op != "Mul" or len(m.inputs) != 2:
+            continue
+        for inner_ref, k_ref in ((m.inputs[0], m.inputs[1]), (m.inputs[1], m.inputs[0])):
+            scale = _one_element(g, k_ref, 1.0 / 6.0, HARD_SCALE_REL)
+            if scale is None:
+                continue
+            hit = _relu6_of_x_plus_3(g, c, inner_ref, m)
+            if hit is not None:
+                x_ref, inner = hit
+                _finalize(g, inner + [m], "_HardSigmoid", [x_ref], {"scale": scale})
+                c.refresh()
+                break
+            # slim: the outer Mul scales Mul(x, Relu6(x + 3))
+            i = g.nodes.get(inner_ref[0])
+            if i is None or inner_ref[1] != 0 or i.op != "Mul" or len(i.inputs) != 2 or c.only_consumer(i.name) is not m:
+                continue
+            for x_ref, r_ref in ((i.inputs[0], i.inputs[1]), (i.inputs[1], i.inputs[0])):
+                hit = _relu6_of_x_plus_3(g, c, r_ref, i)
+                if hit is not None and hit[0] == x_ref:
+                    _finalize(g, hit[1] + [i, m], "_HardSwish", [x_ref], {"scale": scale})
+                    c.refresh()
+                    break
+            if m.op != "Mul":
+                break
+    for name in order:
+        m = g.nodes.get(name)
+        if m is None or m.op != "Mul" or len(m.inputs) != 2:
+            continue
+        for x_ref, s_ref in ((m.inputs[0], m.inputs[1]), (m.inputs[1], m.inputs[0])):
+            s = g.nodes.get(s_ref[0])
+            if s is None or s_ref[1] != 0 or s.op != "_HardSigmoid" or s.inputs[0] != x_ref or \
+                    c.only_consumer(s.name) is not m:
+                continue
+            _finalize(g, [s, m], "_HardSwish", [x_ref], {"scale": s.attr("scale", 1.0 / 6.0)})
+            c.refresh()
+            break
+
+
+# ------------------------------------------------------------------ squeeze-and-excite
+class SqueezeExcite:
+    """``x * hard_sigmoid(act1(mean_hw(x) w1 + b1) w2 + b2)`` with the gate
+    broadcast over H and W.  w1 [C][Cr], w2 [Cr][C]: the TF 1x1 filters reshaped
+    [Cin][Cout]; they and the biases stay fp32 on both paths.  On the GPU two
+    launches, ``se_gate`` then ``se_scale`` (kernels/se.hip), which use 1/6 for
+    the gate's scale; the reference path multiplies by the graph's constant.
+    What depends on the rank is decided per call: an ``x`` that is not rank 4
+    gets the original nodes' semantics from torch."""
+
+    def __init__(self, w1, b1, w2, b2, act1: str, scale: float, keep_dims: bool, axes, reshape, device, use_hip: bool,
+                 name: str):
+        self.c, self.cr = w1.shape
+        self.act1 = act1
+        self.scale = float(scale)
+        self.keep = keep_dims
+        self.axes = tuple(int(a) for a in axes)
+        self.reshape = None if reshape is None else [int(v) for v in reshape]
+        self.use_hip = use_hip
+        self.name = name
+        self.device = device
+        self.w1 = to_device(w1.float().contiguous(), device)
+        self.b1 = to_device(b1.float().contiguous(), device)
+        self.w2 = to_device(w2.float().contiguous(), device)
+        self.b2 = to_device(b2.float().contiguous(), device)
+        # se_gate masks its idle FC lanes by feeding 0 to an FMA against a real weight: an Inf / NaN
+        # weight would reach gates it has no part in, so such a model keeps the torch path
+        if self.use_hip and not all(t.is_meta or bool(torch.isfinite(t).all()) for t in (w1, b1, w2, b2)):
+            self.use_hip = False
+
+    def _params(self, dev):
+        return (t.to(dev) for t in (self.w1, self.b1, self.w2, self.b2))
+
+    def _original(self, x):
+        """The matched nodes one by one (Mean, [Reshape], Conv2D + bias, act1,
+        Conv2D + bias, hard-sigmoid, Mul) for an x the kernels do not take."""
+        w1, b1, w2, b2 = self._params(x.device)
+        xf = x.float()
+        p = xf.mean(dim=sorted({a % x.dim() for a in self.axes}), keepdim=self.keep)
+        if self.reshape is not None:
+            p = p.reshape(self.reshape)
+
+        def conv1x1(t, w):
+            return F.conv2d(t.permute(0, 3, 1, 2), w.t().reshape(w.shape[1], w.shape[0], 1, 1)).permute(0, 2, 3, 1)
+        h = _ref_act(conv1x1(p, w1) + b1, self.act1)
+        gate = torch.clamp(conv1x1(h, w2) + b2 + 3.0, 0.0, 6.0) * self.scale
+        return xf * gate
+
+    def __call__(self, ctx, node, ins):
+        x = O.to_torch(ins[0])
+        if x.dim() != 4 or x.shape[3] != self.c:
+            y = self._original(x)
+            return [y.to(BF16) if x.dtype == BF16 else y]
+        if self.use_hip and x.is_cuda:
+            from ..ops import ACT, hip
+            H = hip()
+            if H.se_gate_supported(x.shape[0], x.shape[1] * x.shape[2], self.c, self.cr) and x.numel() > 0:
+                xb = _to_bf16(x).contiguous()
+                gate = H.se_gate(xb, self.w1, self.b1, self.w2, self.b2, ACT[self.act1], ACT["hard_sigmoid"])
+                return [H.se_scale(xb, gate)]
+        w1, b1, w2, b2 = self._params(x.device)
+        xf = x.float()
+        h = _ref_act(xf.mean(dim=(1, 2)) @ w1 + b1, self.act1)
+        gate = torch.clamp(h @ w2 + b2 + 3.0, 0.0, 6.0) * self.scale
+        y = xf * gate[:, None, None, :]
+        return [y.to(BF16) if x.dtype == BF16 else y]
+
+
+def _fc_1x1(g: Graph, n: Optional[Node]):
+    """A Conv2D that is a per-pixel FC (1x1, stride 1, dilation 1, NHWC, no
+    padding, constant 4-D filter) -> its [Cin][Cout] fp32 weight, else None."""
+    if n is None or n.op != "Conv2D" or len(n.inputs) != 2 or n.sattr("data_format", "NHWC") != "NHWC":
+        return None
+    if any(v != 1 for v in (n.attr("dilations", [1, 1, 1, 1]) or [1, 1, 1, 1])) or \
+            any(v != 1 for v in n.attr("strides", [1, 1, 1, 1])) or n.sattr("padding", "VALID") not in ("SAME", "VALID"):
+        return None
+    w = _const(g, n.inputs[1])
+    if w is None or w.dim() != 4 or w.shape[0] != 1 or w.shape[1] != 1:
+        return None
+    return w.float().reshape(w.shape[2], w.shape[3])
+
+
+def fuse_squeeze_excite(g, order, fed, fetch_refs, device, opts):
+    """``Mul(x, g)`` / ``Mul(g, x)`` with ``g = _HardSigmoid([BiasAdd](Conv2D_2(
+    [Relu]([BiasAdd](Conv2D_1(pool(x)))))))`` -> ``_SqueezeExcite(x)``.  ``pool``
+    is a ``_GlobalAvgPool`` over H, W of the very ``x`` being multiplied, with
+    keep_dims, or without and followed by a Reshape to [-1, 1, 1, C]; both
+    convs are per-pixel FCs (``_fc_1x1``) of matching C -> Cr -> C; every node
+    of the gate chain is read once and not fetched.  Runs after fuse_pools and
+    fuse_hard_activations and before fuse_conv, which would otherwise take the
+    FCs and keep only bf16 weights."""
+    c = _Ctx(g, order, fed, fetch_refs, device, opts)
+
+    def up(ref, reader, ops):
+        """The node behind ``ref`` if it is one of ``ops`` (output 0) read by ``reader`` alone."""
+        n = g.nodes.get(ref[0])
+        if n is None or ref[1] != 0 or n.op not in ops or c.only_consumer(n.name) is not reader:
+            return None
+        return n
+
+    def fc(ref, reader):
+        """([BiasAdd ->] Conv2D chain nodes reader-side first, conv, w, bias) behind ``ref``."""
+        nodes = []
+        ba = up(ref, reader, ("BiasAdd",))
+        bias = None
+        if ba is not None:
+            bias = _const(g, ba.inputs[1])
+            if bias is None or bias.dim() != 1 or ba.sattr("data_format", "NHWC") != "NHWC":
+                return None
+            nodes.append(ba)
+            ref, reader = ba.inputs[0], ba
+        conv = up(ref, reader, ("Conv2D",))
+        w = _fc_1x1(g, conv)
+        if w is None or (bias is not None and bias.numel() != w.shape[1]):
+            return None
+        nodes.append(conv)
+        return nodes, conv, w, bias if bias is not None else zeros(w.shape[1], w)
+
+    for name in order:
+        m = g.nodes.get(name)
+        if m is None or m.op != "Mul" or len(m.inputs) != 2:
+            continue
+        for x_ref, g_ref in ((m.inputs[0], m.inputs[1]), (m.inputs[1], m.inputs[0])):
+            hs = up(g_ref, m, ("_HardSigmoid",))
+            if hs is None or x_ref == g_ref:
+                continue
+            f2 = fc(hs.inputs[0], hs)
+            if f2 is None:
+                continue
+            nodes2, conv2, w2, b2 = f2
+            act1, reader, ref = "none", conv2, conv2.inputs[0]
+            chain = [hs] + nodes2
+            relu = up(ref, conv2, ("Relu",))
+            if relu is not None:
+                act1, reader, ref = "relu", relu, relu.inputs[0]
+                chain.append(relu)
+            f1 = fc(ref, reader)
+            if f1 is None:
+                continue
+            nodes1, conv1, w1, b1 = f1
+            chain += nodes1
+            ch, cr = w1.shape
+            if tuple(w2.shape) != (cr, ch):
+                continue
+            reshape = None
+            ref, reader = conv1.inputs[0], conv1
+            rs = up(ref, conv1, ("Reshape",))
+            if rs is not None:
+                shp = _const(g, rs.inputs[1])
+                if shp is None or [int(v) for v in shp.reshape(-1).tolist()] != [-1, 1, 1, ch]:
+                    continue
+                reshape = [-1, 1, 1, ch]
+                chain.append(rs)
+                ref, reader = rs.inputs[0], rs
+            pool = up(ref, reader, ("_GlobalAvgPool",))
+            if pool is None or pool.inputs[0] != x_ref:
+                continue
+            pimpl = pool.attrs["_impl"]
+            if not isinstance(pimpl, GlobalAvgPool) or pimpl.keep == (reshape is not None):
+                continue
+            chain.append(pool)
+            impl = SqueezeExcite(w1, b1, w2, b2, act1, hs.attr("scale", 1.0 / 6.0), pimpl.keep, pimpl.axes, reshape,
+                                 device, c.use_hip, m.name)
+            _finalize(g, chain[::-1] + [m], "_SqueezeExcite", [x_ref], {"_impl": impl})
+            c.refresh()
+            break
 
 
 def _feeds_head(c: _Ctx, name: str, depth: int = 0) -> bool:
@@ -1530,8 +1817,8 @@ def fuse_dual_conv(g, order, fed, fetch_refs, device, opts):
         b = r.attrs["_impl"]
         if not (_is_1x1(a) and _is_1x1(b)) or b.act != "none" or c.only_consumer(r.name) is not n:
             continue
-        if a.act == "relu6":
-            continue                  # the dual conv is cgemm-only, and cgemm has no relu6
+        if a.act in IGEMM_ONLY_ACTS:
+            continue                  # the dual conv is cgemm-only, and cgemm has no relu6 / hard_swish
         if a.cin % 64 or b.cin % 64 or a.cout != b.cout or a.cout % 8:
             continue
         # the stride-1 conv's input is the dense source (its rows are the output pixels)
@@ -1673,8 +1960,7 @@ def fuse_conv_chain(g, order, fed, fetch_refs, device, opts):
 
 def default_passes(options=None):
     from .patterns import bert_passes, late_passes
-    return [fuse_pools, fuse_softmax_argmax] + bert_passes() + [fuse_conv, fuse_depthwise, fuse_dual_conv, fuse_post_activation,
-                                                                 fuse_stem_pool, fuse_matmul,
-                                                                 fuse_classifier_head, fuse_dense_softmax,
-                                                                 fuse_conv_chain] + late_passes() + \
+    return [fuse_pools, fuse_softmax_argmax, fuse_hard_activations, fuse_squeeze_excite] + bert_passes() + \
+        [fuse_conv, fuse_depthwise, fuse_dual_conv, fuse_post_activation, fuse_stem_pool, fuse_matmul,
+         fuse_classifier_head, fuse_dense_softmax, fuse_conv_chain] + late_passes() + \
         [fuse_matmul_layernorm, defer_layernorm, release_weight_sources]

@@ -138,13 +138,19 @@ const uint16_t* bf16p(const Tensor& t) { return reinterpret_cast<const uint16_t*
 // their configs is rejected here, and ops.candidates(relu6=True) offers igemm
 // configs only.  The deferred-LayerNorm epilogue has no ReLU6 either, and the
 // post-activation outputs (act2, the max-pool's) are none / ReLU only.
+// Hard-swish (code 7) shares all of this: built where ReLU6 is, rejected where
+// ReLU6 is.  relu6_cfg answers for both "igemm-only" activations.  Hard-sigmoid
+// (code 6) is a gate activation of se.hip: no GEMM / conv epilogue takes it.
 bool relu6_cfg(int64_t cfg) {
   return config_of(cfg) != nullptr && config_of(cfg)->family == tfsk::TileFamily::kIGemm;
 }
 void need_act(int64_t act, int64_t cfg, const char* op) {
-  TORCH_CHECK(act >= tfsk::kActNone && act <= tfsk::kActRelu6, op, ": unknown activation code ", act);
-  TORCH_CHECK(act != tfsk::kActRelu6 || config_of(cfg) == nullptr || relu6_cfg(cfg), op,
-              ": activation relu6 is built into the igemm kernels only (tile config ", cfg, " is not one)");
+  TORCH_CHECK((act >= tfsk::kActNone && act <= tfsk::kActRelu6) || act == tfsk::kActHardSwish, op,
+              ": unknown activation code ", act);
+  const bool igemm_only = act == tfsk::kActRelu6 || act == tfsk::kActHardSwish;
+  TORCH_CHECK(!igemm_only || config_of(cfg) == nullptr || relu6_cfg(cfg), op, ": activation ",
+              act == tfsk::kActRelu6 ? "relu6" : "hard_swish", " is built into the igemm kernels only (tile config ",
+              cfg, " is not one)");
 }
 void need_post_act(int64_t act, const char* op) {
   TORCH_CHECK(act == tfsk::kActNone || act == tfsk::kActRelu, op, ": the post activation is none (0) or relu (1), got ",
@@ -354,7 +360,7 @@ std::vector<Tensor> linear_lnx(const Tensor& x, const Tensor& w, const c10::opti
                                const c10::optional<Tensor>& r_st, const c10::optional<Tensor>& r_gamma,
                                const c10::optional<Tensor>& r_beta, double r_eps, bool stats) {
   TORCH_CHECK(act >= tfsk::kActNone && act <= tfsk::kActTanh, "linear_lnx: unknown activation code ", act,
-              " (the deferred-LayerNorm epilogue has no relu6)");
+              " (the deferred-LayerNorm epilogue has no relu6 and no hard_swish)");
   need(x, at::kBFloat16, "x");
   need(w, at::kBFloat16, "w");
   c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
@@ -492,8 +498,8 @@ Tensor maxpool(const Tensor& x, int64_t KH, int64_t KW, int64_t SH, int64_t SW, 
 Tensor dwconv2d(const Tensor& x, const Tensor& w, const Tensor& bias, int64_t KH, int64_t KW, int64_t SH, int64_t SW,
                 int64_t PT, int64_t PL, int64_t Ho, int64_t Wo, int64_t act, const c10::optional<Tensor>& out,
                 int64_t strip) {
-  TORCH_CHECK(act == tfsk::kActNone || act == tfsk::kActRelu || act == tfsk::kActRelu6,
-              "dwconv2d: the activation is none (0), relu (1) or relu6 (5), got ", act);
+  TORCH_CHECK(act == tfsk::kActNone || act == tfsk::kActRelu || act == tfsk::kActRelu6 || act == tfsk::kActHardSwish,
+              "dwconv2d: the activation is none (0), relu (1), relu6 (5) or hard_swish (7), got ", act);
   need(x, at::kBFloat16, "x");
   need(w, at::kFloat, "w");
   need(bias, at::kFloat, "bias");
@@ -520,6 +526,64 @@ Tensor dwconv2d(const Tensor& x, const Tensor& w, const Tensor& bias, int64_t KH
   check(tfsk::dwconv_nhwc_launch(bf16p(x), w.data_ptr<float>(), bias.data_ptr<float>(), bf16p_mut(y), int(N), int(H),
                                  int(W), int(C), int(KH), int(KW), int(SH), int(SW), int(PT), int(PL), int(Ho), int(Wo),
                                  int(act), int(strip), cur_stream(x)), "dwconv2d");
+  return y;
+}
+
+// Squeeze-and-excite gate (se.hip): x NHWC bf16, w1 [C][Cr], b1 [Cr], w2 [Cr][C],
+// b2 [C] f32 (the TF 1x1 filters reshaped [Cin][Cout]) -> gate [B][C] f32 =
+// gate_act(act1(mean_hw(x) w1 + b1) w2 + b2).
+Tensor se_gate(const Tensor& x, const Tensor& w1, const Tensor& b1, const Tensor& w2, const Tensor& b2, int64_t act1,
+               int64_t gate_act, const c10::optional<Tensor>& out) {
+  TORCH_CHECK(act1 == tfsk::kActNone || act1 == tfsk::kActRelu, "se_gate: act1 is none (0) or relu (1), got ", act1);
+  TORCH_CHECK(gate_act == tfsk::kActHardSigmoid, "se_gate: gate_act is hard_sigmoid (6), got ", gate_act);
+  need(x, at::kBFloat16, "x");
+  need(w1, at::kFloat, "w1");
+  need(b1, at::kFloat, "b1");
+  need(w2, at::kFloat, "w2");
+  need(b2, at::kFloat, "b2");
+  TORCH_CHECK(x.dim() == 4, "se_gate: x must be NHWC");
+  const int64_t B = x.size(0), HW = x.size(1) * x.size(2), C = x.size(3);
+  TORCH_CHECK(C % 8 == 0 && C >= 8 && C <= tfsk::kSeMaxC, "se_gate: C % 8 == 0 and 8 <= C <= ", tfsk::kSeMaxC,
+              " (got ", C, " channels)");
+  TORCH_CHECK(w1.dim() == 2 && w1.size(0) == C, "se_gate: w1 must be [C][Cr]");
+  const int64_t Cr = w1.size(1);
+  TORCH_CHECK(Cr >= 1 && Cr <= tfsk::kSeMaxCr, "se_gate: 1 <= Cr <= ", tfsk::kSeMaxCr, " (got ", Cr, ")");
+  TORCH_CHECK(HW >= 1, "se_gate: H * W >= 1 (empty image)");
+  TORCH_CHECK(b1.dim() == 1 && b1.size(0) == Cr, "se_gate: b1 must be [Cr]");
+  TORCH_CHECK(w2.dim() == 2 && w2.size(0) == Cr && w2.size(1) == C, "se_gate: w2 must be [Cr][C]");
+  TORCH_CHECK(b2.dim() == 1 && b2.size(0) == C, "se_gate: b2 must be [C]");
+  TORCH_CHECK(x.numel() * 2 < 0x7ffffff0LL, "se_gate: x must be < 2 GiB");
+  TORCH_CHECK(w1.device() == x.device() && b1.device() == x.device() && w2.device() == x.device() &&
+              b2.device() == x.device(), "se_gate: tensors on different devices");
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
+  Tensor g = out.has_value() ? *out : torch::empty({B, C}, x.options().dtype(at::kFloat));
+  need(g, at::kFloat, "out");
+  TORCH_CHECK(g.numel() == B * C && g.device() == x.device(), "out has the wrong size");
+  TORCH_CHECK(aligned16(x) && aligned16(w1) && aligned16(b1) && aligned16(w2) && aligned16(b2) && aligned16(g),
+              "se_gate: tensors must be 16-B aligned");
+  check(tfsk::se_gate_launch(bf16p(x), w1.data_ptr<float>(), b1.data_ptr<float>(), w2.data_ptr<float>(),
+                             b2.data_ptr<float>(), g.data_ptr<float>(), int(B), int(HW), int(C), int(Cr), int(act1),
+                             int(gate_act), cur_stream(x)), "se_gate");
+  return g;
+}
+
+// y = bf16(x * gate[b][c]): x NHWC bf16 (C % 8 == 0), gate [B][C] f32.
+Tensor se_scale(const Tensor& x, const Tensor& gate, const c10::optional<Tensor>& out) {
+  need(x, at::kBFloat16, "x");
+  need(gate, at::kFloat, "gate");
+  TORCH_CHECK(x.dim() == 4 && x.size(3) >= 8 && x.size(3) % 8 == 0, "se_scale: NHWC with C % 8 == 0 (got ",
+              x.dim() == 4 ? x.size(3) : -1, " channels)");
+  const int64_t B = x.size(0), HW = x.size(1) * x.size(2), C = x.size(3);
+  TORCH_CHECK(HW >= 1, "se_scale: H * W >= 1 (empty image)");
+  TORCH_CHECK(gate.numel() == B * C && gate.device() == x.device(), "se_scale: gate must be [B][C]");
+  TORCH_CHECK(x.numel() * 2 < 0x7ffffff0LL, "se_scale: x must be < 2 GiB");
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
+  Tensor y = out.has_value() ? *out : torch::empty_like(x);
+  need(y, at::kBFloat16, "out");
+  TORCH_CHECK(y.numel() == x.numel() && y.device() == x.device(), "out has the wrong size");
+  TORCH_CHECK(aligned16(x) && aligned16(gate) && aligned16(y), "se_scale: tensors must be 16-B aligned");
+  check(tfsk::se_scale_launch(bf16p(x), gate.data_ptr<float>(), bf16p_mut(y), int(B), int(HW), int(C), cur_stream(x)),
+        "se_scale");
   return y;
 }
 
@@ -965,6 +1029,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
                            int64_t sw) {
     return tfsk::dwconv_strip(int(n), int(ho), int(wo), int(c), int(kh), int(kw), int(sh), int(sw));
   }, "output rows per thread dwconv2d picks by itself (0: the generic kernel, which has no strips)");
+  m.def("se_gate", &se_gate, "squeeze-excite gate [B][C] f32: gate_act(act1(mean_hw(x) w1 + b1) w2 + b2)",
+        py::arg("x"), py::arg("w1"), py::arg("b1"), py::arg("w2"), py::arg("b2"), py::arg("act1") = 1,
+        py::arg("gate_act") = 6, py::arg("out") = py::none());
+  m.def("se_scale", &se_scale, "bf16(x * gate[b][c]), NHWC bf16 x, [B][C] f32 gate", py::arg("x"), py::arg("gate"),
+        py::arg("out") = py::none());
+  m.def("se_gate_supported", [](int64_t b, int64_t hw, int64_t c, int64_t cr) {
+    return tfsk::se_gate_supported(b, hw, c, cr);
+  }, "whether se_gate takes B images of HW pixels, C channels and Cr hidden units");
   m.def("global_avgpool", &global_avgpool, py::arg("x"), py::arg("out") = py::none());
   m.def("classifier_head", &classifier_head, "softmax/argmax(mean_hw(x) @ w^T + bias)[:, :n]", py::arg("x"),
         py::arg("w"), py::arg("bias"), py::arg("n"));

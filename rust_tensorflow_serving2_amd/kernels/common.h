@@ -16,7 +16,11 @@ constexpr int kWave = 64;
 constexpr int kNumXcd = 8;
 
 enum Act : int { kActNone = 0, kActRelu = 1, kActGeluTanh = 2, kActGeluErf = 3, kActTanh = 4,
-                 kActRelu6 = 5 };
+                 kActRelu6 = 5,
+                 // hard-sigmoid clamp(x + 3, 0, 6) / 6: a gate activation (se.hip), no GEMM / conv epilogue
+                 kActHardSigmoid = 6,
+                 // hard-swish x * hard_sigmoid(x): dwconv.hip, igemm.hip and the split-K reduce
+                 kActHardSwish = 7 };
 
 __device__ __forceinline__ float bf16_to_f32(bf16_t v) {
   return __uint_as_float(uint32_t(v) << 16);
@@ -47,6 +51,9 @@ __device__ __forceinline__ float gelu_tanh(float x) {
   return x * __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(x * t));
 }
 
+// clamp(x + 3, 0, 6) * (1/6): one add, two clamps, one product
+__device__ __forceinline__ float hard_sigmoid(float x) { return fminf(fmaxf(x + 3.f, 0.f), 6.f) * (1.f / 6.f); }
+
 __device__ __forceinline__ float apply_act(float x, int act) {
   switch (act) {
     case kActRelu: return x > 0.f ? x : 0.f;
@@ -54,6 +61,8 @@ __device__ __forceinline__ float apply_act(float x, int act) {
     case kActGeluErf: return 0.5f * x * (1.f + erff(x * 0.7071067811865476f));
     case kActTanh: return 2.f * sigm2(x) - 1.f;
     case kActRelu6: return fminf(fmaxf(x, 0.f), 6.f);
+    case kActHardSigmoid: return hard_sigmoid(x);
+    case kActHardSwish: return x * hard_sigmoid(x);
     default: return x;
   }
 }
@@ -72,6 +81,10 @@ __device__ __forceinline__ float act_fn(float x) {
     return 2.f * sigm2(x) - 1.f;
   } else if constexpr (ACT == kActRelu6) {
     return fminf(fmaxf(x, 0.f), 6.f);
+  } else if constexpr (ACT == kActHardSigmoid) {
+    return hard_sigmoid(x);
+  } else if constexpr (ACT == kActHardSwish) {
+    return x * hard_sigmoid(x);
   } else {
     return x;
   }

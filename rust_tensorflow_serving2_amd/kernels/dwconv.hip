@@ -2,7 +2,8 @@
 // multiplier 1: y[n][ho][wo][c] = act(bias[c] + sum_{kh,kw} x[n][ho*SH-PT+kh][wo*SW-PL+kw][c] * w[kh*KW+kw][c]).
 // The filter ([KH*KW][C], BatchNorm folded in) and the bias stay fp32; the
 // accumulation is one fp32 FMA per tap on top of the bias, then the
-// activation and one round-to-nearest-even store to bf16.
+// activation (none, ReLU, ReLU6 or hard-swish) and one round-to-nearest-even
+// store to bf16.
 //
 // The op is bandwidth-bound (KH*KW FMAs per 2 bytes in and 2 bytes out), so
 // the 3x3 kernels are built around one read of the input and one write of the
@@ -216,6 +217,9 @@ void launch3x3(const DwArgs& a, int act, dim3 grid, hipStream_t s) {
   switch (act) {
     case kActRelu: hipLaunchKernelGGL((dwconv3x3_kernel<S, R, kActRelu>), grid, dim3(kThreads), 0, s, a); break;
     case kActRelu6: hipLaunchKernelGGL((dwconv3x3_kernel<S, R, kActRelu6>), grid, dim3(kThreads), 0, s, a); break;
+    case kActHardSwish:
+      hipLaunchKernelGGL((dwconv3x3_kernel<S, R, kActHardSwish>), grid, dim3(kThreads), 0, s, a);
+      break;
     default: hipLaunchKernelGGL((dwconv3x3_kernel<S, R, kActNone>), grid, dim3(kThreads), 0, s, a); break;
   }
 }
@@ -235,7 +239,7 @@ int dwconv_strip(int N, int Ho, int Wo, int C, int KH, int KW, int SH, int SW, i
 hipError_t dwconv_nhwc_launch(const uint16_t* x, const float* w, const float* bias, uint16_t* y, int N, int H, int W,
                               int C, int KH, int KW, int SH, int SW, int PT, int PL, int Ho, int Wo, int act,
                               int strip, hipStream_t s) {
-  if (act != kActNone && act != kActRelu && act != kActRelu6) return hipErrorInvalidValue;
+  if (act != kActNone && act != kActRelu && act != kActRelu6 && act != kActHardSwish) return hipErrorInvalidValue;
   if (C <= 0 || C % 8 || KH < 1 || KW < 1 || KH > kMaxTaps || KW > kMaxTaps || SH < 1 || SW < 1 || PT < 0 || PL < 0 ||
       H <= 0 || W <= 0 || N < 0 || Ho < 0 || Wo < 0 || (strip != 0 && strip != kDwStripShort && strip != kDwStripTall))
     return hipErrorInvalidValue;
@@ -252,6 +256,9 @@ hipError_t dwconv_nhwc_launch(const uint16_t* x, const float* w, const float* bi
     switch (act) {
       case kActRelu: hipLaunchKernelGGL(dwconv_generic_kernel<kActRelu>, grid, dim3(kThreads), 0, s, a); break;
       case kActRelu6: hipLaunchKernelGGL(dwconv_generic_kernel<kActRelu6>, grid, dim3(kThreads), 0, s, a); break;
+      case kActHardSwish:
+        hipLaunchKernelGGL(dwconv_generic_kernel<kActHardSwish>, grid, dim3(kThreads), 0, s, a);
+        break;
       default: hipLaunchKernelGGL(dwconv_generic_kernel<kActNone>, grid, dim3(kThreads), 0, s, a); break;
     }
   } else if (SH == 1) {

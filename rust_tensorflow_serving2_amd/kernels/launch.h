@@ -166,7 +166,7 @@ hipError_t maxpool_nhwc_launch(const uint16_t* x, uint16_t* y, int N, int H, int
                                int act = 0);
 // NHWC bf16 depthwise conv, channel multiplier 1 (dwconv.hip): x [N][H][W][C]
 // (C % 8 == 0), w [KH*KW][C] f32, bias [C] f32 -> y [N][Ho][Wo][C] bf16 =
-// act(conv + bias), act in {kActNone, kActRelu, kActRelu6}; KH, KW <= 7,
+// act(conv + bias), act in {kActNone, kActRelu, kActRelu6, kActHardSwish}; KH, KW <= 7,
 // explicit top / left padding, Ho / Wo from the caller (taps outside the image
 // read zero).  3x3 with stride 1 or 2 runs the strip kernels, `strip` output
 // rows per thread (kDwStripShort, kDwStripTall, or 0: dwconv_strip's rule);
@@ -176,6 +176,20 @@ int dwconv_strip(int N, int Ho, int Wo, int C, int KH, int KW, int SH, int SW, i
 hipError_t dwconv_nhwc_launch(const uint16_t* x, const float* w, const float* bias, uint16_t* y, int N, int H, int W,
                               int C, int KH, int KW, int SH, int SW, int PT, int PL, int Ho, int Wo, int act,
                               int strip, hipStream_t stream);
+// Squeeze-and-excite (se.hip), two launches per block.
+// se_gate: x [B][HW][C] bf16 (NHWC, C % 8 == 0, 8 <= C <= kSeMaxC) ->
+// gate [B][C] f32 = gate_act(act1(mean_hw(x) w1 + b1) w2 + b2), all in fp32.
+// The weights are the TF 1x1 filters as they are, row-major [Cin][Cout] f32:
+// w1 [C][Cr], b1 [Cr], w2 [Cr][C], b2 [C], 1 <= Cr <= kSeMaxCr.  act1 is
+// kActNone or kActRelu, gate_act kActHardSigmoid.  One workgroup per image;
+// x must be < 2 GiB.  se_gate_supported: the shape limits alone.
+// se_scale: y [B][HW][C] bf16 = bf16(x * gate[b][c]) (C % 8 == 0, x < 2 GiB).
+constexpr int kSeMaxC = 2048, kSeMaxCr = 512;
+bool se_gate_supported(long B, long HW, long C, long Cr);
+hipError_t se_gate_launch(const uint16_t* x, const float* w1, const float* b1, const float* w2, const float* b2,
+                          float* gate, int B, int HW, int C, int Cr, int act1, int gate_act, hipStream_t stream);
+hipError_t se_scale_launch(const uint16_t* x, const float* gate, uint16_t* y, int B, int HW, int C,
+                           hipStream_t stream);
 // Mean over H,W of NHWC bf16 -> [N][C] (bf16).
 hipError_t global_avgpool_nhwc_launch(const uint16_t* x, uint16_t* y, int N, int HW, int C,
                                       hipStream_t stream);

@@ -51,7 +51,11 @@ def available() -> bool:
         return False
 
 
-ACT = {"none": 0, "relu": 1, "gelu_tanh": 2, "gelu_erf": 3, "tanh": 4, "relu6": 5}   # kernels/common.h Act
+ACT = {"none": 0, "relu": 1, "gelu_tanh": 2, "gelu_erf": 3, "tanh": 4, "relu6": 5,
+       "hard_sigmoid": 6, "hard_swish": 7}   # kernels/common.h Act
+# the activations only the igemm kernels (and the split-K reduce) implement: their launches
+# pass relu6=True (or its alias igemm_act=True) to candidates / tuned_config
+IGEMM_ONLY_ACTS = ("relu6", "hard_swish")
 
 # ------------------------------------------------------------------ autotune
 _TUNED: Dict[Tuple, int] = {}
@@ -194,7 +198,7 @@ def heuristic_splits(M: int, N: int, K: int, cfg: int) -> int:
 
 def candidates(M: int, N: int, K: int, dma: bool = True, aligned64: bool = False, cgemm_only: bool = False,
                halo: bool = False, no_split: bool = False, stem: bool = False, ln: bool = False,
-               relu6: bool = False):
+               relu6: bool = False, igemm_act: bool = False):
     """(tile config, split-K) pairs worth timing for an M x N x K problem
     (``dma``: the operand mode uses the direct-to-LDS path, so the deeper
     DMA-ring configs apply; ``aligned64``: K and the conv channels are
@@ -202,8 +206,9 @@ def candidates(M: int, N: int, K: int, dma: bool = True, aligned64: bool = False
     stride-1 conv with C % 64 == 0, so the halo-tiled configs apply too —
     their split-K granule is a 64-channel chunk of 9 taps; ``stem``: the
     padded RGBA stem operand, which the 32-deep and persistent builds do not
-    take; ``relu6``: the launch's activation is ReLU6, which only the igemm
-    kernels implement)."""
+    take; ``relu6``: the launch's activation is ReLU6 or hard-swish, which only
+    the igemm kernels implement; ``igemm_act`` is an alias of it)."""
+    relu6 = relu6 or igemm_act
     nk = -(-K // 64)
     out = []
     if halo and aligned64 and K % 576 == 0 and N % 8 == 0 and not relu6:
@@ -230,7 +235,7 @@ def candidates(M: int, N: int, K: int, dma: bool = True, aligned64: bool = False
         if cgemm_only and cfg not in CGEMM:
             continue
         if relu6 and cfg in CGEMM:
-            continue   # ReLU6 is an igemm epilogue only (the bindings reject it elsewhere)
+            continue   # ReLU6 / hard-swish are igemm epilogues only (the bindings reject them elsewhere)
         if cfg in BGEMM and (stem or ln or not PINGPONG):
             continue   # dense operands, plain epilogues only
         if ln and (cfg not in CGEMM or bn % 32):
@@ -354,11 +359,12 @@ def _time_concurrent(launch: Callable[[int, int], None], cands, conc: int, flush
 def tuned_config(key: Tuple, M: int, N: int, launch: Callable[[int, int], None], K: int = 64,
                  dma: bool = True, aligned64: bool = False, cgemm_only: bool = False,
                  halo: bool = False, no_split: bool = False, stem: bool = False,
-                 ln: bool = False, relu6: bool = False) -> Tuple[int, int]:
+                 ln: bool = False, relu6: bool = False, igemm_act: bool = False) -> Tuple[int, int]:
     """Pick the fastest (tile config, split-K) for ``key`` by timing each
     candidate (eager only — never during HIP-graph capture, where the
     heuristic is used).  Inside ``tuning_regime(k > 1)`` the pick is the
     best aggregate throughput at k concurrent streams, under its own key."""
+    relu6 = relu6 or igemm_act
     key = regime_key(key)
     conc = getattr(_REGIME, "conc", 1)
     rec = getattr(_REC, "keys", None)

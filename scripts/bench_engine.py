@@ -19,28 +19,40 @@ def main():
     ap.add_argument("--batch", type=int, nargs="+", default=[1, 32])
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--baseline", action="store_true")
-    ap.add_argument("--model", default="resnet50", choices=["resnet50", "resnet50-v2", "mobilenet-v1", "mobilenet-v2", "bert-base"])
+    ap.add_argument("--model", default="resnet50", choices=["resnet50", "resnet50-v2", "mobilenet-v1", "mobilenet-v2", "mobilenet-v3-large",
+                                                      "mobilenet-v3-small", "bert-base"])
     ap.add_argument("--graph-tune", type=int, default=1, help="whole-graph tile re-tuning at capture (0 = off)")
+    ap.add_argument("--windows", type=int, default=1,
+                    help="timed windows of --iters replays each; above 1, graph_ms is their median and "
+                         "graph_ms_windows lists them")
+    ap.add_argument("--model-dir", help="serve this SavedModel version directory instead of exporting one "
+                                        "(the same bytes for two trees, e.g. this one and its parent commit)")
+    ap.add_argument("--ops", action="store_true", help="also print the fused program's op histogram")
     args = ap.parse_args()
     import logging
     logging.basicConfig(level=logging.INFO, format="%(name)s: %(message)s")
     from rust_tensorflow_serving2_amd.models import bert, resnet
     from rust_tensorflow_serving2_amd.server.servable import Servable, ServableOptions
-    path = os.path.join(tempfile.mkdtemp(), "1")
+    path = args.model_dir or os.path.join(tempfile.mkdtemp(), "1")
     opts = ServableOptions(device="cuda:0", max_batch_size=max(args.batch), graph_autotune=bool(args.graph_tune))
     if args.model == "bert-base":
-        bert.export(path, seed=0)
+        if not args.model_dir:
+            bert.export(path, seed=0)
         s = Servable("bert", 1, path, opts)
         r = s.runner("serving_default", ["input_ids", "input_mask", "segment_ids"], ["pooled_output", "probabilities"])
         flop_per_item = 2 * 85e6 * 128 + 4 * 12 * 128 * 128 * 768   # encoder GEMMs + attention, seq 128
     elif args.model.startswith("mobilenet"):
         from rust_tensorflow_serving2_amd.models import mobilenet
-        mobilenet.export(path, version=args.model.split("-")[1])
+        if not args.model_dir:
+            mobilenet.export(path, version=args.model.split("-", 1)[1].replace("-", "_"))
         s = Servable("mobilenet", 1, path, opts)
         r = s.runner("serving_default", ["input"], ["classes", "probabilities"])
-        flop_per_item = 2 * (569e6 if args.model == "mobilenet-v1" else 300e6)    # multiply-adds at 224 x 224
+        # multiply-adds at 224 x 224
+        flop_per_item = 2 * {"mobilenet-v1": 569e6, "mobilenet-v2": 300e6, "mobilenet-v3-large": 219e6,
+                             "mobilenet-v3-small": 56e6}[args.model]
     else:
-        resnet.export(path, version="v2" if args.model == "resnet50-v2" else "v1.5")
+        if not args.model_dir:
+            resnet.export(path, version="v2" if args.model == "resnet50-v2" else "v1.5")
         s = Servable("resnet", 1, path, opts)
         r = s.runner("serving_default", ["input"], ["classes", "probabilities"])
         flop_per_item = 2 * 4.1e9
@@ -61,11 +73,14 @@ def main():
         for _ in range(5):
             g.replay()
         torch.cuda.synchronize()
-        t = time.perf_counter()
-        for _ in range(args.iters):
-            g.replay()
-        torch.cuda.synchronize()
-        dt = (time.perf_counter() - t) / args.iters
+        windows = []
+        for _ in range(max(1, args.windows)):
+            t = time.perf_counter()
+            for _ in range(args.iters):
+                g.replay()
+            torch.cuda.synchronize()
+            windows.append((time.perf_counter() - t) / args.iters)
+        dt = float(np.median(windows))
         # full runner path: H2D + replay + D2H
         t = time.perf_counter()
         for _ in range(args.iters // 2):
@@ -73,7 +88,11 @@ def main():
         dt_full = (time.perf_counter() - t) / (args.iters // 2)
         res[b] = {"graph_ms": dt * 1e3, "img_per_s": b / dt, "run_ms": dt_full * 1e3,
                   "tflops": flop_per_item * b / dt / 1e12, "capture_s": round(t_capture, 2)}
+        if args.windows > 1:
+            res[b]["graph_ms_windows"] = [round(w * 1e3, 4) for w in windows]
         print(json.dumps({"model": args.model, "batch": b, **res[b]}), flush=True)
+    if args.ops:
+        print(json.dumps({"model": args.model, "ops": dict(r.program.op_histogram())}), flush=True)
     if args.baseline and args.model == "resnet50":
         baseline(args)
 

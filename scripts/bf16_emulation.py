@@ -1,0 +1,112 @@
+#!/usr/bin/env python
+"""What does bf16 storage alone cost a MobileNet end to end?  CPU only.
+
+Exports a random-init MobileNet, runs the fp32 interpreter, and runs the fused
+CPU program a second time with the conv weights rounded to bf16 and the output of
+every fused conv / depthwise / squeeze-excite op rounded to bf16 -- what the GPU
+program stores -- with everything else in fp32.  Prints, per input seed:
+
+* the fp32 interpreter's logit spread per row, its top-1 / top-2 margin, the
+  margin a row needs to be decidable (3 x 0.05 x spread) and how many rows are
+  (the rule tests/test_mobilenet_v3_gpu.py picks its input seed by);
+* how far the logits follow the image: std over the batch / spread over classes;
+* the emulated logit error / logit spread per row, the figure the end-to-end GPU
+  tests hold under 0.05.  Trial 0 is plain rounding; further trials multiply each
+  value by 1 + u * 2^-9, u uniform in (-1/2, 1/2), before rounding: another sample
+  of the rounding errors, as another summation order would give.
+
+`--gated-gain` / `--expand-gain` override models/mobilenet.py's init gains
+(V3_GATED_PROJECT_GAIN / V3_EXPAND_GAIN) for the exported model.
+
+    python scripts/bf16_emulation.py --version v3_small --seeds 0 1 2 3 --trials 3
+"""
+import argparse
+import os
+import sys
+import tempfile
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from rust_tensorflow_serving2_amd.models import mobilenet  # noqa: E402
+from rust_tensorflow_serving2_amd.server.servable import Servable, ServableOptions  # noqa: E402
+
+OUTS = ["classes", "probabilities"]
+ROUNDED = ("_FusedConv2D", "_FusedDepthwiseConv2D", "_SqueezeExcite")
+
+
+def bf16(t):
+    return t.to(torch.bfloat16).float()
+
+
+def centred_logits(probs):
+    lg = np.log(np.maximum(probs, 1e-30)).astype(np.float64)
+    return lg - lg.mean(1, keepdims=True)
+
+
+def emulate(program, trial):
+    """Round the fused ops' weights and outputs to bf16 in place; `trial[0]` selects the noise sample."""
+    steps = []
+    for fn, node, ins, outs in program.steps:
+        if node.op in ROUNDED:
+            impl = node.attrs.get("_impl")
+            if hasattr(impl, "w_ref"):
+                impl.w_ref = bf16(impl.w_ref)
+
+            def rounded(ctx, node, vals, fn=fn):
+                res = []
+                for y in fn(ctx, node, vals):
+                    if trial[0]:
+                        gen = torch.Generator().manual_seed(trial[0] * 1000 + len(res))
+                        y = y * (1 + (torch.rand(y.shape, generator=gen) - 0.5) * 2.0 ** -9)
+                    res.append(bf16(y))
+                return res
+            steps.append((rounded, node, ins, outs))
+        else:
+            steps.append((fn, node, ins, outs))
+    program.steps = steps
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--version", default="v3_small", choices=mobilenet.VERSIONS)
+    ap.add_argument("--image-size", type=int, default=64)
+    ap.add_argument("--model-seed", type=int, default=3)
+    ap.add_argument("--batch", type=int, default=3)
+    ap.add_argument("--seeds", type=int, nargs="+", default=[0, 1, 2, 3])
+    ap.add_argument("--trials", type=int, default=3)
+    ap.add_argument("--gated-gain", type=float)
+    ap.add_argument("--expand-gain", type=float)
+    a = ap.parse_args()
+    if a.gated_gain is not None:
+        mobilenet.V3_GATED_PROJECT_GAIN = dict(mobilenet.V3_GATED_PROJECT_GAIN, **{a.version: a.gated_gain})
+    if a.expand_gain is not None:
+        mobilenet.V3_EXPAND_GAIN = dict(mobilenet.V3_EXPAND_GAIN, **{a.version: a.expand_gain})
+    if a.version.startswith("v3"):
+        print(a.version, "gated project gain", mobilenet.V3_GATED_PROJECT_GAIN[a.version], "expand gain",
+              mobilenet.V3_EXPAND_GAIN[a.version])
+    path = os.path.join(tempfile.mkdtemp(), "1")
+    mobilenet.export(path, version=a.version, image_size=a.image_size, seed=a.model_seed)
+    ref = Servable("m", 1, path, ServableOptions(device="cpu"))
+    emu = Servable("m", 1, path, ServableOptions(device="cpu", fuse=True))
+    trial = [0]
+    emulate(emu.runner("serving_default", ["input"], OUTS).program, trial)
+    np.set_printoptions(precision=4, suppress=True)
+    for s in a.seeds:
+        x = np.random.default_rng(s).random((a.batch, a.image_size, a.image_size, 3), dtype=np.float32)
+        lc = centred_logits(ref.run("serving_default", {"input": x}, OUTS)["probabilities"])
+        spread = lc.std(1)
+        top2 = np.sort(lc, 1)[:, -2:]
+        margin = top2[:, 1] - top2[:, 0]
+        print(f"{a.version} input seed {s} spread {spread} margin {margin} need {0.15 * spread} "
+              f"ok rows {int((margin > 0.15 * spread).sum())}  image dependence {lc.std(0).mean() / spread.mean():.3f}")
+        xb = bf16(torch.from_numpy(x)).numpy()
+        for t in range(a.trials):
+            trial[0] = t
+            lg = centred_logits(emu.run("serving_default", {"input": xb}, OUTS)["probabilities"])
+            print(f"    trial {t} emulated logit error / spread {np.abs(lg - lc).max(1) / spread}")
+
+
+if __name__ == "__main__":
+    main()

@@ -5,12 +5,13 @@ The reference downloads ``resnet_v2_fp32_savedmodel_NHWC`` and copies version
 Offline, we write random-init SavedModels of the same architectures in the
 same ``<root>/<name>/<version>/`` layout:
 
-    python serving/make_models.py --root serving/models [--models resnet,resnet_v2,mobilenet,mobilenet_v2,bert,half_plus_two]
+    python serving/make_models.py --root serving/models [--models resnet,resnet_v2,mobilenet,mobilenet_v2,mobilenet_v3_large,mobilenet_v3_small,bert,half_plus_two]
 
 * ``resnet``        ResNet-50 v1.5 (NHWC, alias "input", outputs classes/probabilities)
 * ``resnet_v2``     ResNet-50 v2 pre-activation (the fetch.sh model's architecture)
 * ``mobilenet``     MobileNet V1 1.0 224 (slim layout: SAME depthwise convs, ReLU6)
 * ``mobilenet_v2``  MobileNet V2 1.0 224 (Keras layout: Pad + VALID on stride 2, linear bottlenecks)
+* ``mobilenet_v3_large`` / ``mobilenet_v3_small``  MobileNetV3 1.0 224 (Keras layout: hard-swish, squeeze-excite)
 * ``bert``          BERT-base seq 128 (input_ids / input_mask / segment_ids)
 * ``half_plus_two`` TF Serving's canonical test model
 
@@ -41,9 +42,10 @@ def main(argv=None):
             resnet.export(out, seed=args.seed)
         elif m == "resnet_v2":
             resnet.export(out, seed=args.seed, version="v2")
-        elif m in ("mobilenet", "mobilenet_v2"):
+        elif m in ("mobilenet", "mobilenet_v2", "mobilenet_v3_large", "mobilenet_v3_small"):
             from rust_tensorflow_serving2_amd.models import mobilenet
-            mobilenet.export(out, version="v2" if m == "mobilenet_v2" else "v1", seed=args.seed)
+            version = {"mobilenet": "v1", "mobilenet_v2": "v2"}.get(m, m[len("mobilenet_"):])
+            mobilenet.export(out, version=version, seed=args.seed)
         elif m == "bert":
             from rust_tensorflow_serving2_amd.models import bert
             bert.export(out, bert.BertConfig(), seed=args.seed)
