@@ -19,6 +19,10 @@ a single consumer and is not fetched):
   => ``_FusedDepthwiseConv2D`` (channel multiplier 1): BN folded into the fp32
   filter, one ``dwconv2d`` launch (kernels/dwconv.hip).  ``Relu6`` also fuses
   into ``_FusedConv2D`` (MobileNet's pointwise convs).
+* ``[Pad] -> Conv2D -> [BiasAdd] -> [FusedBatchNorm*] -> [Relu]`` whose input has a
+  known multiple of the filter's in-depth channels (a grouped conv: ResNeXt)
+  => ``_FusedGroupedConv2D``: BN folded, one ``gconv2d`` launch (kernels/gconv.hip)
+  for 3x3 filters with 4 / 8 / 16 / 32 channels per group.
 * ``MatMul -> [BiasAdd] -> [Add(residual)] -> [Relu|Tanh|GELU]`` => ``_FusedMatMul``
   (fp32 output when it feeds a Softmax/ArgMax head or is fetched).
 * ``Mean(NHWC, axes=[1,2])`` => ``_GlobalAvgPool``;  ``MaxPool`` => ``_MaxPool``;
@@ -233,10 +237,36 @@ class FusedConv:
             return tuple(self.pads)
         return (0, 0, 0, 0)
 
+    def _hwio(self) -> torch.Tensor:
+        """The folded filter as fp32 HWIO, from whichever form this op keeps."""
+        if not self.use_hip:
+            return self.w_ref
+        if self.c4:
+            w = self.w[:, :self.khp * 32].reshape(self.cout, self.khp, 8, 4)[:, :self.kh, :self.kw, :self.cin]
+        else:
+            w = self.w[:, :self.kh * self.kw * self.cin].reshape(self.cout, self.kh, self.kw, self.cin)
+        return w.float().permute(1, 2, 3, 0)
+
+    def _other_depth(self, x, res, pads):
+        """The input has another channel count than the filter's in-depth (the
+        pass could not see it): Conv2D's own semantics with torch -- a grouped
+        conv when the counts divide, else torch's error, which the executor
+        reports as the interpreter's Conv2D does."""
+        pt, pb, pl, pr = pads
+        w = self._hwio().to(x.device)
+        b = (self.b if self.use_hip else self.b_ref).to(x.device)
+        y = _grouped_conv_torch(x.float(), w, b, (self.sh, self.sw), (pt, pb, pl, pr), x.shape[3] // self.cin)
+        if res is not None:
+            y = y + res.float()
+        outs = _with_post(self, _ref_act(y, self.act).contiguous())
+        return [o.to(BF16) for o in outs] if self.use_hip else outs
+
     def __call__(self, ctx, node, ins):
         x = O.to_torch(ins[0])
         res = O.to_torch(ins[1]) if len(ins) > 1 else None
         pt, pb, pl, pr = self.pads_for(x.shape[1], x.shape[2])
+        if x.shape[3] != self.cin:
+            return self._other_depth(x, res, (pt, pb, pl, pr))
         if not self.use_hip:
             y = F.conv2d(F.pad(x.float().permute(0, 3, 1, 2), [pl, pr, pt, pb]),
                          self.w_ref.permute(3, 2, 0, 1), stride=(self.sh, self.sw))
@@ -351,6 +381,107 @@ class FusedDepthwiseConv:
         key = ("dwconv", tuple(x.shape), self.kh, self.kw, self.sh, self.sw, pt, pl, ho, wo, self.act)
         pick = tuned_choice(key, {2: lambda: run(2), 8: lambda: run(8)}, default=auto)
         return [run(pick)]
+
+
+def _grouped_conv_torch(x: torch.Tensor, w_hwio: torch.Tensor, bias: torch.Tensor, strides, pads, groups: int):
+    """NHWC ``conv2d(pad(x), w, groups=) + bias`` in the dtype of ``x`` (the
+    interpreter's Conv2D, ops._conv2d: the same calls, so the same errors)."""
+    pt, pb, pl, pr = pads
+    xc = x.permute(0, 3, 1, 2)
+    xc = F.pad(xc, [pl, pr, pt, pb]) if (pt or pb or pl or pr) else xc
+    y = F.conv2d(xc, w_hwio.to(x.dtype).permute(3, 2, 0, 1), stride=tuple(strides), groups=groups)
+    return y.permute(0, 2, 3, 1) + bias.to(x.dtype)
+
+
+GCONV_CG = (4, 8, 16, 32)         # kernels/gconv.hip: channels per group, in == out
+
+
+def gconv_ksteps(cg: int) -> int:
+    """32-deep MFMA k-steps per output (kernels/launch.h gconv_ksteps)."""
+    return (9 * cg + 31) // 32
+
+
+def pack_grouped_filter(w_hwio: torch.Tensor, cg: int) -> torch.Tensor:
+    """The [3][3][cg][C] filter of a grouped conv with cg outputs per group, as
+    bf16 in the MFMA fragment order of kernels/gconv.hip (launch.h):
+    [C / cg groups][k-steps][column tiles][64 lanes][8], element j of lane l =
+    B[k = 32 ks + 8 (l >> 4) + j][col = 16 nt + (l & 15)] with k = tap * cg +
+    channel; zeros where k >= 9 cg (the K padding) and where col >= cg."""
+    kh, kw, ci, c = w_hwio.shape
+    assert (kh, kw, ci) == (3, 3, cg) and c % cg == 0 and cg in GCONV_CG
+    g, ks, nt = c // cg, gconv_ksteps(cg), 2 if cg == 32 else 1
+    b = torch.zeros(g, ks * 32, nt * 16, dtype=torch.float32, device=w_hwio.device)
+    b[:, :9 * cg, :cg] = w_hwio.float().reshape(9 * cg, g, cg).permute(1, 0, 2)
+    # [g][ks][q][j][nt][m] -> [g][ks][nt][q][m][j], lane = 16 q + m
+    b = b.reshape(g, ks, 4, 8, nt, 16).permute(0, 1, 4, 2, 5, 3)
+    return b.contiguous().to(BF16).reshape(-1)
+
+
+class FusedGroupedConv:
+    """Grouped Conv2D (a filter whose in-depth is C / groups)(+folded BN/bias)(+act
+    none | relu).  The fp32 HWIO filter serves the CPU reference and the torch
+    paths; the kernel (kernels/gconv.hip: 3x3, equal strides 1 | 2, cg inputs
+    and outputs per group, cg in 4 | 8 | 16 | 32) reads it packed as bf16 MFMA
+    fragments.  Any other shape runs torch's grouped conv on the device."""
+
+    def __init__(self, w_hwio: torch.Tensor, bias: torch.Tensor, strides, padding: str, pads, act: str,
+                 device: torch.device, use_hip: bool, name: str, channels: int):
+        self.kh, self.kw, self.cg, self.cout = w_hwio.shape
+        self.c = channels                           # input channels the pass saw: groups * cg
+        self.groups = channels // self.cg
+        self.cgo = self.cout // self.groups
+        self.sh, self.sw = strides
+        self.padding = padding          # "SAME" | "VALID" | "EXPLICIT"
+        self.pads = pads                # (pt, pb, pl, pr) for EXPLICIT
+        self.act = act
+        self.use_hip = use_hip
+        self.name = name
+        self.device = device
+        self.kernel = use_hip and self.hip_ok(self.kh, self.kw, self.cg, self.cgo, channels, strides)
+        self.b = to_device(bias.float(), device)
+        if self.kernel:
+            self.w = to_device(pack_grouped_filter(w_hwio, self.cg), device)
+        else:
+            self.w_ref = to_device(w_hwio.float().contiguous(), device)
+
+    @staticmethod
+    def hip_ok(kh: int, kw: int, cg_in: int, cg_out: int, c: int, strides) -> bool:
+        """What kernels/gconv.hip takes (launch.h gconv_supported)."""
+        return (kh == 3 and kw == 3 and cg_in == cg_out and cg_in in GCONV_CG and c % 8 == 0 and c % cg_in == 0 and
+                strides[0] == strides[1] and strides[0] in (1, 2))
+
+    pads_for = FusedConv.pads_for
+
+    def _hwio(self) -> torch.Tensor:
+        if hasattr(self, "w_ref"):
+            return self.w_ref
+        # back from the fragments (bf16 values): [g][ks][nt][q][m][j] -> [g][k][col]
+        g, ks, nt = self.groups, gconv_ksteps(self.cg), 2 if self.cg == 32 else 1
+        b = self.w.float().reshape(g, ks, nt, 4, 16, 8).permute(0, 1, 3, 5, 2, 4).reshape(g, ks * 32, nt * 16)
+        return b[:, :9 * self.cg, :self.cg].permute(1, 0, 2).reshape(3, 3, self.cg, self.cout)
+
+    def _torch(self, x, pads):
+        """Conv2D's own semantics for this input (ops._conv2d: groups from the
+        input's channel count), fp32 accumulation; bf16 out on the device."""
+        xf = x.float()
+        y = _grouped_conv_torch(xf, self._hwio().to(x.device), self.b.to(x.device), (self.sh, self.sw), pads,
+                                x.shape[3] // self.cg)
+        y = _ref_act(y, self.act).contiguous()
+        return [y.to(BF16) if self.use_hip else y]
+
+    def __call__(self, ctx, node, ins):
+        x = O.to_torch(ins[0])
+        pads = self.pads_for(x.shape[1], x.shape[2])
+        if not self.kernel or x.shape[3] != self.c or os.environ.get("TFSERVE_GCONV", "1") == "0":
+            return self._torch(x, pads)
+        from ..ops import ACT, hip
+        pt, pb, pl, pr = pads
+        n, h, w, _ = x.shape
+        ho = (h + pt + pb - 3) // self.sh + 1
+        wo = (w + pl + pr - 3) // self.sh + 1
+        x = _to_bf16(x).contiguous()
+        out = torch.empty((n, ho, wo, self.cout), device=x.device, dtype=BF16)
+        return [hip().gconv2d(x, self.w, self.b, self.cg, self.sh, pt, pl, ho, wo, ACT[self.act], out)]
 
 
 class FusedDualConv:
@@ -855,7 +986,7 @@ def _impl_op(ctx, node, ins):
     return node.attrs["_impl"](ctx, node, ins)
 
 
-for _op in ("_FusedConv2D", "_FusedDepthwiseConv2D", "_FusedDualConv", "_FusedMatMul", "_GlobalAvgPool", "_MaxPool",
+for _op in ("_FusedConv2D", "_FusedDepthwiseConv2D", "_FusedGroupedConv2D", "_FusedDualConv", "_FusedMatMul", "_GlobalAvgPool", "_MaxPool",
             "_SqueezeExcite",
             "_SoftmaxArgMax", "_LayerNorm",
             "_FusedQKV", "_Attention", "_EmbeddingLN", "_KeyMaskAdder", "_DenseSoftmax"):
@@ -1228,6 +1359,147 @@ def fuse_stem_pool(g, order, fed, fetch_refs, device, opts):
         c.refresh()
 
 
+# ops whose output has the channel count of input 0 (NHWC pools included)
+_SAME_CHANNELS = ("Identity", "StopGradient", "Snapshot", "Relu", "Relu6", "Elu", "Selu", "LeakyRelu", "Sigmoid",
+                  "Tanh", "Softplus", "Neg", "Abs", "Square", "Sqrt", "Rsqrt", "Exp", "Cast", "_HardSwish",
+                  "_HardSigmoid", "_SqueezeExcite", "MaxPool", "AvgPool", "_MaxPool")
+_BATCH_NORMS = ("FusedBatchNorm", "FusedBatchNormV2", "FusedBatchNormV3")
+
+
+def _channels_of(g: Graph, ref, fed=frozenset(), depth: int = 64, seen: Optional[Set] = None) -> Optional[int]:
+    """The NHWC channel count (last dimension) of the value ``ref``, read off
+    its producers' constants, or None.  The compiler infers no shapes and
+    Conv2D has no ``groups`` attribute: this is how the passes tell a grouped
+    conv from a dense one.  A count from here is what the graph declares; the
+    fused ops still check the tensor they are given."""
+    seen = set() if seen is None else seen
+    n = g.nodes.get(ref[0])
+    if n is None or depth <= 0 or ref in seen:
+        return None
+    seen.add(ref)
+    if n.op == "Placeholder":
+        shape = n.attrs.get("shape")
+        return int(shape[-1]) if ref[1] == 0 and shape and len(shape) == 4 and shape[-1] > 0 else None
+    if ref[0] in fed or ref[1] != 0:
+        return None
+    if n.op in ("_FusedConv2D", "_FusedGroupedConv2D", "_FusedDualConv"):
+        return int(n.attrs["_impl"].cout)
+    if n.op == "_FusedDepthwiseConv2D":
+        return int(n.attrs["_impl"].c)
+    nhwc = n.sattr("data_format", "NHWC") == "NHWC"
+    if n.op in ("Conv2D", "DepthwiseConv2dNative") and nhwc:
+        w = _const(g, n.inputs[1])
+        if w is None or w.dim() != 4:
+            return None
+        return int(w.shape[3]) if n.op == "Conv2D" else int(w.shape[2] * w.shape[3])
+    if (n.op in _BATCH_NORMS or n.op == "BiasAdd") and nhwc:
+        v = _const(g, n.inputs[1])
+        return int(v.numel()) if v is not None and v.dim() == 1 else None
+    if n.op in _SAME_CHANNELS and nhwc and n.inputs:
+        return _channels_of(g, n.inputs[0], fed, depth - 1, seen)
+    if n.op == "Pad" and len(n.inputs) == 2:
+        pv = _const(g, n.inputs[1])
+        if pv is None or tuple(pv.shape) != (4, 2) or int(pv[3, 0]) or int(pv[3, 1]):
+            return None
+        return _channels_of(g, n.inputs[0], fed, depth - 1, seen)
+    if n.op in ("Add", "AddV2", "Mul") and len(n.inputs) == 2:
+        # whichever operand resolves; a 1 may be broadcast against the other operand
+        got = {_channels_of(g, r, fed, depth - 1, seen) for r in n.inputs} - {None}
+        wide = got - {1}
+        return wide.pop() if len(wide) == 1 else None
+    return None
+
+
+def _absorb_pad(g: Graph, c: _Ctx, n: Node, x_ref, padding: str, pads, chain: List[Node]):
+    """A spatial ``Pad`` in front of a VALID conv ``n`` (its only consumer)
+    becomes the conv's explicit padding: (x_ref, padding, pads), the Pad
+    appended to ``chain``."""
+    prod = g.nodes.get(x_ref[0])
+    if (padding == "VALID" and prod is not None and prod.op == "Pad" and x_ref[1] == 0
+            and c.only_consumer(prod.name) is n):
+        pv = _const(g, prod.inputs[1])
+        if pv is not None:
+            p = [int(v) for v in pv.reshape(-1).tolist()]
+            if len(p) == 8 and p[0] == p[1] == p[6] == p[7] == 0 and min(p) >= 0:
+                chain.append(prod)
+                return prod.inputs[0], "EXPLICIT", (p[2], p[3], p[4], p[5])
+    return x_ref, padding, pads
+
+
+def fuse_grouped_conv(g, order, fed, fetch_refs, device, opts):
+    """``[Pad ->] Conv2D [-> BiasAdd] [-> FusedBatchNorm*] [-> Relu]`` ->
+    ``_FusedGroupedConv2D`` where the conv is a GROUPED one: the channel count
+    of its input (``_channels_of``) is known and a proper multiple of the
+    filter's in-depth, which is above 1 (in-depth 1 is a depthwise conv spelled
+    as Conv2D: it stays on the reference op).  fuse_conv's guards apply (NHWC,
+    dilation 1, a constant 4-D filter, an inference BatchNorm whose only used
+    output is y, no fetch inside the chain, single consumers).  No residual
+    ``Add`` is absorbed (the kernel reads none), and a closing activation other
+    than Relu stays a node of its own.  3x3 filters with 4 / 8 / 16 / 32
+    inputs and outputs per group run kernels/gconv.hip on the GPU, any other
+    shape torch's grouped conv on the device.
+
+    Runs directly before fuse_conv, which skips what this pass left for the
+    same reason (a known channel count that differs from the in-depth).  The
+    later passes (fuse_dual_conv, fuse_post_activation, fuse_stem_pool,
+    fuse_conv_chain, the late passes) look for ``_FusedConv2D`` by op name, so
+    ``_FusedGroupedConv2D`` is opaque to them: it is never a dual-conv half, a
+    post-activation producer or a chain link."""
+    c = _Ctx(g, order, fed, fetch_refs, device, opts)
+    for name in order:
+        n = g.nodes.get(name)
+        if n is None or n.op != "Conv2D" or n.sattr("data_format", "NHWC") != "NHWC":
+            continue
+        dil = n.attr("dilations", [1, 1, 1, 1]) or [1, 1, 1, 1]
+        if any(d != 1 for d in dil):
+            continue
+        w = _const(g, n.inputs[1])
+        if w is None or w.dim() != 4 or w.shape[2] <= 1:
+            continue
+        cg, cout = int(w.shape[2]), int(w.shape[3])
+        ch = _channels_of(g, n.inputs[0], fed)
+        if ch is None or ch == cg or ch % cg or cout % (ch // cg):
+            continue
+        padding = n.sattr("padding", "VALID")
+        pads = (0, 0, 0, 0)
+        chain: List[Node] = []
+        if padding == "EXPLICIT":
+            ep = n.attr("explicit_paddings", [])
+            if ep[0] or ep[1] or ep[6] or ep[7]:
+                continue
+            pads = (ep[2], ep[3], ep[4], ep[5])
+        x_ref, padding, pads = _absorb_pad(g, c, n, n.inputs[0], padding, pads, chain)
+        strides = n.attr("strides", [1, 1, 1, 1])
+        w = w.float()
+        bias = zeros(cout, w)
+        chain.append(n)
+        cur = n
+        act = "none"
+        nxt = c.only_consumer(cur.name)
+        if nxt is not None and nxt.op == "BiasAdd" and nxt.inputs[0] == (cur.name, 0):
+            b = _const(g, nxt.inputs[1])
+            if b is not None and tuple(b.shape) == (cout,):
+                bias = bias + b.float()
+                chain.append(nxt)
+                cur = nxt
+                nxt = c.only_consumer(cur.name)
+        if nxt is not None and nxt.op in _BATCH_NORMS and nxt.inputs[0] == (cur.name, 0):
+            aff = _bn_affine(g, c, nxt)
+            if aff is not None and aff[0].numel() == cout:
+                w = w * aff[0]
+                bias = bias * aff[0] + aff[1]
+                chain.append(nxt)
+                cur = nxt
+                nxt = c.only_consumer(cur.name)
+        if nxt is not None and nxt.op == "Relu":
+            act = "relu"
+            chain.append(nxt)
+            cur = nxt
+        impl = FusedGroupedConv(w, bias, (strides[1], strides[2]), padding, pads, act, device, c.use_hip, cur.name, ch)
+        _finalize(g, chain, "_FusedGroupedConv2D", [x_ref], {"_impl": impl})
+        c.refresh()
+
+
 def fuse_conv(g, order, fed, fetch_refs, device, opts):
     c = _Ctx(g, order, fed, fetch_refs, device, opts)
     for name in order:
@@ -1239,6 +1511,11 @@ def fuse_conv(g, order, fed, fetch_refs, device, opts):
             continue
         w = _const(g, n.inputs[1])
         if w is None or w.dim() != 4:
+            continue
+        # a grouped conv (Conv2D has no groups attribute: its input has more channels than the filter's
+        # in-depth) is fuse_grouped_conv's, or stays on the reference op; an input whose channel count
+        # the graph does not tell is checked by FusedConv when it runs
+        if _channels_of(g, n.inputs[0], fed) not in (None, int(w.shape[2])):
             continue
         x_ref = n.inputs[0]
         padding = n.sattr("padding", "VALID")
@@ -1961,6 +2238,6 @@ def fuse_conv_chain(g, order, fed, fetch_refs, device, opts):
 def default_passes(options=None):
     from .patterns import bert_passes, late_passes
     return [fuse_pools, fuse_softmax_argmax, fuse_hard_activations, fuse_squeeze_excite] + bert_passes() + \
-        [fuse_conv, fuse_depthwise, fuse_dual_conv, fuse_post_activation, fuse_stem_pool, fuse_matmul,
+        [fuse_grouped_conv, fuse_conv, fuse_depthwise, fuse_dual_conv, fuse_post_activation, fuse_stem_pool, fuse_matmul,
          fuse_classifier_head, fuse_dense_softmax, fuse_conv_chain] + late_passes() + \
         [fuse_matmul_layernorm, defer_layernorm, release_weight_sources]

@@ -529,6 +529,45 @@ Tensor dwconv2d(const Tensor& x, const Tensor& w, const Tensor& bias, int64_t KH
   return y;
 }
 
+// Grouped 3x3 conv (gconv.hip): x NHWC bf16, w the bf16 filter in MFMA fragment
+// order (launch.h: gconv_packed_elems(C, cg) elements, graph/fused.py
+// pack_grouped_filter), bias [C] f32 -> act(conv + bias) as [N][Ho][Wo][C] bf16.
+// cg inputs and cg_out outputs per group (cg_out < 0: cg), strides sh x sw (sw
+// < 0: sh), a kh x kw filter.  What the kernel does not take -- launch.h
+// gconv_supported, an act other than none / relu -- is the launcher's
+// hipErrorInvalidValue, raised here before anything is written.
+Tensor gconv2d(const Tensor& x, const Tensor& w, const Tensor& bias, int64_t cg, int64_t SH, int64_t PT, int64_t PL,
+               int64_t Ho, int64_t Wo, int64_t act, const c10::optional<Tensor>& out, int64_t cg_out, int64_t SW,
+               int64_t KH, int64_t KW) {
+  need(x, at::kBFloat16, "x");
+  need(w, at::kBFloat16, "w");
+  need(bias, at::kFloat, "bias");
+  TORCH_CHECK(x.dim() == 4 && x.size(3) > 0, "gconv2d: x must be NHWC");
+  if (cg_out < 0) cg_out = cg;
+  if (SW < 0) SW = SH;
+  const int64_t N = x.size(0), H = x.size(1), W = x.size(2), C = x.size(3);
+  TORCH_CHECK(H >= 1 && W >= 1 && PT >= 0 && PL >= 0 && Ho >= 1 && Wo >= 1, "gconv2d: bad geometry");
+  TORCH_CHECK(cg >= 1 && cg_out >= 1 && cg <= 4096 && cg_out <= 4096 && SH >= 1 && SW >= 1 && SH <= 64 && SW <= 64 &&
+              KH >= 1 && KW >= 1 && KH <= 64 && KW <= 64, "gconv2d: bad filter geometry");
+  // the last window must start inside the padded image: no output made of padding alone
+  TORCH_CHECK((Ho - 1) * SH - PT < H && (Wo - 1) * SW - PL < W, "gconv2d: output larger than the input allows");
+  TORCH_CHECK(bias.numel() == C, "gconv2d: bias must have C entries");
+  TORCH_CHECK(w.device() == x.device() && bias.device() == x.device(), "gconv2d: tensors on different devices");
+  const bool ok = tfsk::gconv_supported(int(C), int(cg), int(cg_out), int(KH), int(KW), int(SH), int(SW));
+  TORCH_CHECK(!ok || w.numel() == tfsk::gconv_packed_elems(int(C), int(cg)), "gconv2d: w must hold ",
+              ok ? tfsk::gconv_packed_elems(int(C), int(cg)) : 0, " packed elements, got ", w.numel());
+  TORCH_CHECK(x.numel() * 2 < 0x7ffffff0LL && N * Ho * Wo * C * 2 < 0x7ffffff0LL, "gconv2d operands must be < 2 GiB");
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
+  Tensor y = out.has_value() ? *out : torch::empty({N, Ho, Wo, C}, x.options());
+  need(y, at::kBFloat16, "out");
+  TORCH_CHECK(y.numel() == N * Ho * Wo * C && y.device() == x.device(), "out has the wrong size");
+  TORCH_CHECK(aligned16(x) && aligned16(w) && aligned16(bias) && aligned16(y), "gconv2d: tensors must be 16-B aligned");
+  check(tfsk::gconv_nhwc_launch(bf16p(x), bf16p(w), bias.data_ptr<float>(), bf16p_mut(y), int(N), int(H), int(W), int(C),
+                                int(cg), int(cg_out), int(KH), int(KW), int(SH), int(SW), int(PT), int(PL), int(Ho),
+                                int(Wo), int(act), cur_stream(x)), "gconv2d");
+  return y;
+}
+
 // Squeeze-and-excite gate (se.hip): x NHWC bf16, w1 [C][Cr], b1 [Cr], w2 [Cr][C],
 // b2 [C] f32 (the TF 1x1 filters reshaped [Cin][Cout]) -> gate [B][C] f32 =
 // gate_act(act1(mean_hw(x) w1 + b1) w2 + b2).
@@ -1029,6 +1068,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
                            int64_t sw) {
     return tfsk::dwconv_strip(int(n), int(ho), int(wo), int(c), int(kh), int(kw), int(sh), int(sw));
   }, "output rows per thread dwconv2d picks by itself (0: the generic kernel, which has no strips)");
+  m.def("gconv2d", &gconv2d, "grouped 3x3 conv on MFMA: act(conv(x, w packed bf16) + bias), NHWC bf16", py::arg("x"),
+        py::arg("w"), py::arg("bias"), py::arg("cg"), py::arg("sh"), py::arg("pt"), py::arg("pl"), py::arg("ho"),
+        py::arg("wo"), py::arg("act") = 0, py::arg("out") = py::none(), py::arg("cg_out") = -1, py::arg("sw") = -1,
+        py::arg("kh") = 3, py::arg("kw") = 3);
+  m.def("gconv_supported", [](int64_t c, int64_t cg_in, int64_t cg_out, int64_t kh, int64_t kw, int64_t sh,
+                              int64_t sw) {
+    return tfsk::gconv_supported(int(c), int(cg_in), int(cg_out), int(kh), int(kw), int(sh), int(sw));
+  }, "whether gconv2d takes C channels in groups of cg_in inputs / cg_out outputs, a kh x kw filter, strides sh x sw");
+  m.def("gconv_ksteps", [](int64_t cg) { return tfsk::gconv_ksteps(int(cg)); },
+        "32-deep MFMA k-steps gconv2d sums per output (zero-filled padding slots included)");
   m.def("se_gate", &se_gate, "squeeze-excite gate [B][C] f32: gate_act(act1(mean_hw(x) w1 + b1) w2 + b2)",
         py::arg("x"), py::arg("w1"), py::arg("b1"), py::arg("w2"), py::arg("b2"), py::arg("act1") = 1,
         py::arg("gate_act") = 6, py::arg("out") = py::none());

@@ -176,6 +176,24 @@ int dwconv_strip(int N, int Ho, int Wo, int C, int KH, int KW, int SH, int SW, i
 hipError_t dwconv_nhwc_launch(const uint16_t* x, const float* w, const float* bias, uint16_t* y, int N, int H, int W,
                               int C, int KH, int KW, int SH, int SW, int PT, int PL, int Ho, int Wo, int act,
                               int strip, hipStream_t stream);
+// NHWC bf16 grouped 3x3 conv on MFMA (gconv.hip): x [N][H][W][C], bias [C]
+// f32 -> y [N][Ho][Wo][C] bf16 = act(conv_grouped + bias), act in {kActNone,
+// kActRelu}.  CGin == CGout == Cg in {4, 8, 16, 32} channels per group, C % 8
+// == 0, C % Cg == 0, stride 1 or 2 (the same in both directions), explicit top
+// / left padding, Ho / Wo from the caller (taps outside the image read zero).
+// w is the filter in MFMA fragment order, gconv_packed_elems(C, Cg) bf16:
+// [C / Cg groups][gconv_ksteps(Cg)][Cg == 32 ? 2 : 1 column tiles][64 lanes][8],
+// where element j of lane l is B[k = 32 ks + 8 (l >> 4) + j][col = 16 nt + (l & 15)]
+// = w_hwio[tap k / Cg][k % Cg][g Cg + col], and zero where k >= 9 Cg or col >= Cg.
+// Anything else (gconv_supported is false, another act, operands of 2 GiB or
+// more) returns hipErrorInvalidValue and launches nothing.
+constexpr int kGconvSlab = 32;                 // channels of a workgroup's LDS halo
+constexpr int gconv_ksteps(int cg) { return (9 * cg + 31) / 32; }    // 32-deep MFMA k-steps per output
+bool gconv_supported(int C, int CGin, int CGout, int KH, int KW, int SH, int SW);
+long gconv_packed_elems(int C, int CG);
+hipError_t gconv_nhwc_launch(const uint16_t* x, const uint16_t* w, const float* bias, uint16_t* y, int N, int H, int W,
+                             int C, int CGin, int CGout, int KH, int KW, int SH, int SW, int PT, int PL, int Ho,
+                             int Wo, int act, hipStream_t stream);
 // Squeeze-and-excite (se.hip), two launches per block.
 // se_gate: x [B][HW][C] bf16 (NHWC, C % 8 == 0, 8 <= C <= kSeMaxC) ->
 // gate [B][C] f32 = gate_act(act1(mean_hw(x) w1 + b1) w2 + b2), all in fp32.

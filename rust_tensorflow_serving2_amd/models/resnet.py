@@ -1,4 +1,4 @@
-"""ResNet-50 (v1.5 and v2) SavedModel exporter with random-init weights.
+"""ResNet-50 (v1.5 and v2) and ResNeXt-50 SavedModel exporter with random-init weights.
 
 The graph follows TF's official NHWC ResNet export — the model the reference
 fetches (``serving/fetch.sh:7-9``, ``resnet_v2_fp32_savedmodel_NHWC``):
@@ -53,14 +53,16 @@ def _fixed_pad(g: GraphBuilder, x: str, k: int) -> str:
     return g.node("Pad", "Pad", [x, pads], T=F32, Tpaddings=DType(T.DT_INT32))
 
 
-def _conv(g, init, x, k, cin, cout, stride, name):
+def _conv(g, init, x, k, cin, cout, stride, name, groups=1):
+    """Conv2D; ``groups`` > 1 is TF's grouped form: a filter of in-depth cin / groups
+    (He-normal over its own fan-in) and no attribute that says so."""
     with g.scope(name):
         if stride > 1:
             x = _fixed_pad(g, x, k)
             padding = "VALID"
         else:
             padding = "SAME"
-        w = g.variable("kernel", init.conv(k, k, cin, cout))
+        w = g.variable("kernel", init.conv(k, k, cin // groups, cout))
         return g.node("Conv2D", "Conv2D", [x, w], T=F32, strides=[1, stride, stride, 1],
                       padding=padding, data_format="NHWC", dilations=[1, 1, 1, 1],
                       use_cudnn_on_gpu=True, explicit_paddings=[])
@@ -82,15 +84,16 @@ def _relu(g, x):
     return g.node("Relu", "Relu", [x], T=F32)
 
 
-def _block_v1(g, init, x, cin, filters, stride, project, name):
+def _block_v1(g, init, x, cin, filters, stride, project, name, groups=1, width_per_group=64):
+    inner = filters * width_per_group // 64 * groups        # ResNeXt: 32x4d is 128 / 256 / 512 / 1024
     with g.scope(name):
         shortcut = x
         if project:
             s = _conv(g, init, x, 1, cin, 4 * filters, stride, "shortcut_conv")
             shortcut = _bn(g, init, s, 4 * filters, "shortcut_bn")
-        y = _relu(g, _bn(g, init, _conv(g, init, x, 1, cin, filters, 1, "conv1"), filters, "bn1"))
-        y = _relu(g, _bn(g, init, _conv(g, init, y, 3, filters, filters, stride, "conv2"), filters, "bn2"))
-        y = _bn(g, init, _conv(g, init, y, 1, filters, 4 * filters, 1, "conv3"), 4 * filters, "bn3",
+        y = _relu(g, _bn(g, init, _conv(g, init, x, 1, cin, inner, 1, "conv1"), inner, "bn1"))
+        y = _relu(g, _bn(g, init, _conv(g, init, y, 3, inner, inner, stride, "conv2", groups), inner, "bn2"))
+        y = _bn(g, init, _conv(g, init, y, 1, inner, 4 * filters, 1, "conv3"), 4 * filters, "bn3",
                 gamma_scale=0.25)
         y = g.node("AddV2", "add", [y, shortcut], T=F32)
         return _relu(g, y)
@@ -112,7 +115,12 @@ def _block_v2(g, init, x, cin, filters, stride, project, name):
 
 
 def build_graph(version: str = "v1.5", blocks=BLOCKS_50, num_classes: int = NUM_CLASSES,
-                seed: int = 0, width: int = 64, image_size: int = 224):
+                seed: int = 0, width: int = 64, image_size: int = 224, groups: int = 1,
+                width_per_group: int = 64):
+    """``groups`` / ``width_per_group`` other than 1 / 64 give ResNeXt (v1.5 layout
+    only): 32 / 4 with the default blocks is ResNeXt-50 32x4d."""
+    if (groups, width_per_group) != (1, 64) and version == "v2":
+        raise ValueError("ResNeXt is exported in the v1.5 layout only")
     g = GraphBuilder()
     init = _Init(seed)
     x = g.placeholder("input_tensor", T.DT_FLOAT, [-1, image_size, image_size, 3])
@@ -128,7 +136,8 @@ def build_graph(version: str = "v1.5", blocks=BLOCKS_50, num_classes: int = NUM_
             filters = width * (2 ** si)
             for bi in range(n):
                 stride = 2 if (bi == 0 and si > 0) else 1
-                y = block_fn(g, init, y, cin, filters, stride, bi == 0, f"block_layer{si + 1}_{bi}")
+                kw = {} if version == "v2" else dict(groups=groups, width_per_group=width_per_group)
+                y = block_fn(g, init, y, cin, filters, stride, bi == 0, f"block_layer{si + 1}_{bi}", **kw)
                 cin = 4 * filters
         if version == "v2":
             y = _relu(g, _bn(g, init, y, cin, "postnorm"))
@@ -153,7 +162,31 @@ def build_graph(version: str = "v1.5", blocks=BLOCKS_50, num_classes: int = NUM_
     return g, {"serving_default": sig, "predict": sig}, saver
 
 
+def flop_per_image(blocks=BLOCKS_50, num_classes: int = NUM_CLASSES, width: int = 64, image_size: int = 224,
+                   groups: int = 1, width_per_group: int = 64) -> int:
+    """2 x multiply-adds of the convs and the dense layer of the v1.5 graph
+    build_graph writes, counted layer by layer from the same shapes."""
+    def conv(size, k, cin, cout, g=1):
+        return 2 * size * size * k * k * (cin // g) * cout
+    size = image_size // 2
+    total = conv(size, 7, 3, width)
+    size //= 2                                          # the max-pool
+    cin = width
+    for si, n in enumerate(blocks):
+        filters = width * (2 ** si)
+        inner = filters * width_per_group // 64 * groups
+        for bi in range(n):
+            stride = 2 if (bi == 0 and si > 0) else 1
+            out = size // stride
+            if bi == 0:
+                total += conv(out, 1, cin, 4 * filters)
+            total += conv(size, 1, cin, inner) + conv(out, 3, inner, inner, groups) + conv(out, 1, inner, 4 * filters)
+            size, cin = out, 4 * filters
+    return total + 2 * cin * num_classes
+
+
 def export(export_dir: str, version: str = "v1.5", seed: int = 0, blocks=BLOCKS_50,
-           num_classes: int = NUM_CLASSES, width: int = 64, image_size: int = 224) -> str:
-    g, sigs, saver = build_graph(version, blocks, num_classes, seed, width, image_size)
+           num_classes: int = NUM_CLASSES, width: int = 64, image_size: int = 224, groups: int = 1,
+           width_per_group: int = 64) -> str:
+    g, sigs, saver = build_graph(version, blocks, num_classes, seed, width, image_size, groups, width_per_group)
     return write_saved_model(export_dir, g.graph, sigs, g.variables, g.var_dtypes, saver)

@@ -1,4 +1,4 @@
-"""Engine-level ResNet-50 / MobileNet / BERT timing on one GPU: HIP-graph replay of the fused
+"""Engine-level ResNet-50 / ResNeXt-50 / MobileNet / BERT timing on one GPU: HIP-graph replay of the fused
 program per batch bucket (no transport), plus a torch/MIOpen channels-last
 bf16 baseline of the same network for comparison."""
 import argparse
@@ -19,7 +19,7 @@ def main():
     ap.add_argument("--batch", type=int, nargs="+", default=[1, 32])
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--baseline", action="store_true")
-    ap.add_argument("--model", default="resnet50", choices=["resnet50", "resnet50-v2", "mobilenet-v1", "mobilenet-v2", "mobilenet-v3-large",
+    ap.add_argument("--model", default="resnet50", choices=["resnet50", "resnet50-v2", "resnext50", "mobilenet-v1", "mobilenet-v2", "mobilenet-v3-large",
                                                       "mobilenet-v3-small", "bert-base"])
     ap.add_argument("--graph-tune", type=int, default=1, help="whole-graph tile re-tuning at capture (0 = off)")
     ap.add_argument("--windows", type=int, default=1,
@@ -50,6 +50,12 @@ def main():
         # multiply-adds at 224 x 224
         flop_per_item = 2 * {"mobilenet-v1": 569e6, "mobilenet-v2": 300e6, "mobilenet-v3-large": 219e6,
                              "mobilenet-v3-small": 56e6}[args.model]
+    elif args.model == "resnext50":
+        if not args.model_dir:
+            resnet.export(path, groups=32, width_per_group=4)        # ResNeXt-50 32x4d
+        s = Servable("resnext", 1, path, opts)
+        r = s.runner("serving_default", ["input"], ["classes", "probabilities"])
+        flop_per_item = resnet.flop_per_image(groups=32, width_per_group=4)
     else:
         if not args.model_dir:
             resnet.export(path, version="v2" if args.model == "resnet50-v2" else "v1.5")

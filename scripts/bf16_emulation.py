@@ -1,9 +1,10 @@
 #!/usr/bin/env python
-"""What does bf16 storage alone cost a MobileNet end to end?  CPU only.
+"""What does bf16 storage alone cost a MobileNet (or, with --family resnext, a
+ResNeXt-50 32x4d) end to end?  CPU only.
 
-Exports a random-init MobileNet, runs the fp32 interpreter, and runs the fused
+Exports a random-init model, runs the fp32 interpreter, and runs the fused
 CPU program a second time with the conv weights rounded to bf16 and the output of
-every fused conv / depthwise / squeeze-excite op rounded to bf16 -- what the GPU
+every fused conv / grouped conv / depthwise / squeeze-excite op rounded to bf16 -- what the GPU
 program stores -- with everything else in fp32.  Prints, per input seed:
 
 * the fp32 interpreter's logit spread per row, its top-1 / top-2 margin, the
@@ -19,6 +20,7 @@ program stores -- with everything else in fp32.  Prints, per input seed:
 (V3_GATED_PROJECT_GAIN / V3_EXPAND_GAIN) for the exported model.
 
     python scripts/bf16_emulation.py --version v3_small --seeds 0 1 2 3 --trials 3
+    python scripts/bf16_emulation.py --family resnext --seeds 3 4 --trials 1
 """
 import argparse
 import os
@@ -33,7 +35,7 @@ from rust_tensorflow_serving2_amd.models import mobilenet  # noqa: E402
 from rust_tensorflow_serving2_amd.server.servable import Servable, ServableOptions  # noqa: E402
 
 OUTS = ["classes", "probabilities"]
-ROUNDED = ("_FusedConv2D", "_FusedDepthwiseConv2D", "_SqueezeExcite")
+ROUNDED = ("_FusedConv2D", "_FusedGroupedConv2D", "_FusedDepthwiseConv2D", "_SqueezeExcite")
 
 
 def bf16(t):
@@ -70,6 +72,9 @@ def emulate(program, trial):
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--family", default="mobilenet", choices=["mobilenet", "resnext"],
+                    help="resnext: ResNeXt-50 32x4d at full width (tests/test_resnext_gpu.py's model); --version and "
+                         "the gains are MobileNet's")
     ap.add_argument("--version", default="v3_small", choices=mobilenet.VERSIONS)
     ap.add_argument("--image-size", type=int, default=64)
     ap.add_argument("--model-seed", type=int, default=3)
@@ -83,11 +88,17 @@ def main():
         mobilenet.V3_GATED_PROJECT_GAIN = dict(mobilenet.V3_GATED_PROJECT_GAIN, **{a.version: a.gated_gain})
     if a.expand_gain is not None:
         mobilenet.V3_EXPAND_GAIN = dict(mobilenet.V3_EXPAND_GAIN, **{a.version: a.expand_gain})
-    if a.version.startswith("v3"):
+    if a.family == "resnext":
+        a.version = "resnext50"
+    elif a.version.startswith("v3"):
         print(a.version, "gated project gain", mobilenet.V3_GATED_PROJECT_GAIN[a.version], "expand gain",
               mobilenet.V3_EXPAND_GAIN[a.version])
     path = os.path.join(tempfile.mkdtemp(), "1")
-    mobilenet.export(path, version=a.version, image_size=a.image_size, seed=a.model_seed)
+    if a.family == "resnext":
+        from rust_tensorflow_serving2_amd.models import resnet
+        resnet.export(path, groups=32, width_per_group=4, image_size=a.image_size, seed=a.model_seed)
+    else:
+        mobilenet.export(path, version=a.version, image_size=a.image_size, seed=a.model_seed)
     ref = Servable("m", 1, path, ServableOptions(device="cpu"))
     emu = Servable("m", 1, path, ServableOptions(device="cpu", fuse=True))
     trial = [0]

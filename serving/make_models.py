@@ -5,10 +5,11 @@ The reference downloads ``resnet_v2_fp32_savedmodel_NHWC`` and copies version
 Offline, we write random-init SavedModels of the same architectures in the
 same ``<root>/<name>/<version>/`` layout:
 
-    python serving/make_models.py --root serving/models [--models resnet,resnet_v2,mobilenet,mobilenet_v2,mobilenet_v3_large,mobilenet_v3_small,bert,half_plus_two]
+    python serving/make_models.py --root serving/models [--models resnet,resnet_v2,resnext50,mobilenet,mobilenet_v2,mobilenet_v3_large,mobilenet_v3_small,bert,half_plus_two]
 
 * ``resnet``        ResNet-50 v1.5 (NHWC, alias "input", outputs classes/probabilities)
 * ``resnet_v2``     ResNet-50 v2 pre-activation (the fetch.sh model's architecture)
+* ``resnext50``     ResNeXt-50 32x4d (ResNet-50 v1.5's layout, grouped 3x3 convs: 32 groups)
 * ``mobilenet``     MobileNet V1 1.0 224 (slim layout: SAME depthwise convs, ReLU6)
 * ``mobilenet_v2``  MobileNet V2 1.0 224 (Keras layout: Pad + VALID on stride 2, linear bottlenecks)
 * ``mobilenet_v3_large`` / ``mobilenet_v3_small``  MobileNetV3 1.0 224 (Keras layout: hard-swish, squeeze-excite)
@@ -42,6 +43,8 @@ def main(argv=None):
             resnet.export(out, seed=args.seed)
         elif m == "resnet_v2":
             resnet.export(out, seed=args.seed, version="v2")
+        elif m == "resnext50":
+            resnet.export(out, seed=args.seed, groups=32, width_per_group=4)
         elif m in ("mobilenet", "mobilenet_v2", "mobilenet_v3_large", "mobilenet_v3_small"):
             from rust_tensorflow_serving2_amd.models import mobilenet
             version = {"mobilenet": "v1", "mobilenet_v2": "v2"}.get(m, m[len("mobilenet_"):])
