@@ -15,7 +15,11 @@ a single consumer and is not fetched):
   (MobileNetV3; igemm and dwconv epilogues).
 * ``Mul(x, _HardSigmoid(Conv2D 1x1(act(Conv2D 1x1(_GlobalAvgPool(x))))))`` =>
   ``_SqueezeExcite(x)``: fp32 FC weights, ``se_gate`` + ``se_scale`` (kernels/se.hip).
-* ``[Pad] -> DepthwiseConv2dNative -> [BiasAdd] -> [FusedBatchNorm*] -> [Relu|Relu6|_HardSwish]``
+* ``Mul(x, Sigmoid(x))``, ``Mul(x, Sigmoid(Mul(x, 1.0)))`` and either one behind output 0 of
+  the ``custom_gradient`` ``IdentityN`` => ``_Swish(x)``, a closing activation like
+  ``_HardSwish`` (EfficientNet); the squeeze-excite pattern with a ``Sigmoid`` gate and a none /
+  ``Relu`` / ``_Swish`` inner activation => ``_SqueezeExciteSigmoid(x)``.
+* ``[Pad] -> DepthwiseConv2dNative -> [BiasAdd] -> [FusedBatchNorm*] -> [Relu|Relu6|_HardSwish|_Swish]``
   => ``_FusedDepthwiseConv2D`` (channel multiplier 1): BN folded into the fp32
   filter, one ``dwconv2d`` launch (kernels/dwconv.hip).  ``Relu6`` also fuses
   into ``_FusedConv2D`` (MobileNet's pointwise convs).
@@ -51,9 +55,9 @@ from .ir import Graph, Node
 from .placement import to_device, zeros
 
 BF16 = torch.bfloat16
-IGEMM_ONLY_ACTS = ("relu6", "hard_swish")       # ops.IGEMM_ONLY_ACTS: no cgemm / bgemm / halo epilogue
+IGEMM_ONLY_ACTS = ("relu6", "hard_swish", "swish")    # ops.IGEMM_ONLY_ACTS: no cgemm / bgemm / halo epilogue
 # the ops fuse_conv / fuse_depthwise take as the closing activation -> the kernels' name for it
-_CLOSING_ACTS = {"Relu": "relu", "Relu6": "relu6", "_HardSwish": "hard_swish"}
+_CLOSING_ACTS = {"Relu": "relu", "Relu6": "relu6", "_HardSwish": "hard_swish", "_Swish": "swish"}
 
 
 # ------------------------------------------------------------------ helpers
@@ -376,7 +380,14 @@ class FusedDepthwiseConv:
                               out, strip)
         auto = H.dwconv_strip(n, ho, wo, self.c, self.kh, self.kw, self.sh, self.sw)
         if auto == 0:
-            return [run(0)]         # the generic kernel has one form
+            forms = H.dwconv_forms(n, ho, wo, self.c, self.kh, self.kw, self.sh, self.sw)
+            if len(forms) == 1:
+                return [run(0)]     # the generic kernel has one form
+            # 5x5: the generic kernel or a strip kernel (2 or 4 rows per thread; bit-equal results), timed
+            # per shape; its own key, so a 3x3 entry of the cached table can never answer for it
+            key = ("dwconv5x5", tuple(x.shape), self.sh, self.sw, pt, pl, ho, wo, self.act)
+            pick = tuned_choice(key, {int(f): (lambda f=int(f): run(f)) for f in forms}, default=0)
+            return [run(pick)]
         # output rows per thread (kernels/launch.h kDwStripShort / kDwStripTall), timed per shape
         key = ("dwconv", tuple(x.shape), self.kh, self.kw, self.sh, self.sw, pt, pl, ho, wo, self.act)
         pick = tuned_choice(key, {2: lambda: run(2), 8: lambda: run(8)}, default=auto)
@@ -973,6 +984,10 @@ def _ref_act(y, act):
         return torch.clamp(y + 3.0, 0.0, 6.0) * (1.0 / 6.0)
     if act == "hard_swish":
         return y * (torch.clamp(y + 3.0, 0.0, 6.0) * (1.0 / 6.0))
+    if act == "sigmoid":
+        return torch.sigmoid(y)
+    if act == "swish":
+        return y * torch.sigmoid(y)
     if act == "tanh":
         return torch.tanh(y)
     if act == "gelu_tanh":
@@ -987,7 +1002,7 @@ def _impl_op(ctx, node, ins):
 
 
 for _op in ("_FusedConv2D", "_FusedDepthwiseConv2D", "_FusedGroupedConv2D", "_FusedDualConv", "_FusedMatMul", "_GlobalAvgPool", "_MaxPool",
-            "_SqueezeExcite",
+            "_SqueezeExcite", "_SqueezeExciteSigmoid",
             "_SoftmaxArgMax", "_LayerNorm",
             "_FusedQKV", "_Attention", "_EmbeddingLN", "_KeyMaskAdder", "_DenseSoftmax"):
     O.OPS[_op] = _impl_op
@@ -1362,7 +1377,7 @@ def fuse_stem_pool(g, order, fed, fetch_refs, device, opts):
 # ops whose output has the channel count of input 0 (NHWC pools included)
 _SAME_CHANNELS = ("Identity", "StopGradient", "Snapshot", "Relu", "Relu6", "Elu", "Selu", "LeakyRelu", "Sigmoid",
                   "Tanh", "Softplus", "Neg", "Abs", "Square", "Sqrt", "Rsqrt", "Exp", "Cast", "_HardSwish",
-                  "_HardSigmoid", "_SqueezeExcite", "MaxPool", "AvgPool", "_MaxPool")
+                  "_HardSigmoid", "_SqueezeExcite", "_Swish", "_SqueezeExciteSigmoid", "MaxPool", "AvgPool", "_MaxPool")
 _BATCH_NORMS = ("FusedBatchNorm", "FusedBatchNormV2", "FusedBatchNormV3")
 
 
@@ -1595,7 +1610,7 @@ def fuse_conv(g, order, fed, fetch_refs, device, opts):
 
 
 def fuse_depthwise(g, order, fed, fetch_refs, device, opts):
-    """``[Pad ->] DepthwiseConv2dNative [-> BiasAdd] [-> FusedBatchNorm*] [-> Relu | Relu6 | _HardSwish]``
+    """``[Pad ->] DepthwiseConv2dNative [-> BiasAdd] [-> FusedBatchNorm*] [-> Relu | Relu6 | _HardSwish | _Swish]``
     -> ``_FusedDepthwiseConv2D``, under fuse_conv's guards (NHWC, dilation 1, a
     constant 4-D filter, an inference BatchNorm whose only used output is y, no
     fetch inside the chain, single consumers) and channel multiplier 1.  On the
@@ -1770,10 +1785,64 @@ def fuse_hard_activations(g, order, fed, fetch_refs, device, opts):
             break
 
 
+
+# ------------------------------------------------------------------ swish (EfficientNet)
+def _swish_op(ctx, node, ins):
+    x = O.to_torch(ins[0])
+    xf = x.float()
+    y = xf * torch.sigmoid(xf)
+    return [y.to(x.dtype) if x.dtype == BF16 else y]
+
+
+O.OPS["_Swish"] = _swish_op
+
+
+def fuse_swish(g, order, fed, fetch_refs, device, opts):
+    """``Mul(x, Sigmoid(x))`` and ``Mul(x, Sigmoid(Mul(x, b)))`` with ``b`` a
+    one-element constant exactly 1.0 (TF >= 2.4's swish_impl) -> ``_Swish(x)``;
+    and either one read through output 0 of an ``IdentityN`` whose input 0 is
+    that Mul and whose other outputs have no reader and are not fetched (the
+    custom_gradient wrapper).  fuse_hard_activations' rules: operands in either
+    order, inner nodes read once and not fetched; x may have other readers."""
+    c = _Ctx(g, order, fed, fetch_refs, device, opts)
+    for name in order:
+        m = g.nodes.get(name)
+        if m is None or m.op != "Mul" or len(m.inputs) != 2:
+            continue
+        for x_ref, s_ref in ((m.inputs[0], m.inputs[1]), (m.inputs[1], m.inputs[0])):
+            s = g.nodes.get(s_ref[0])
+            if s is None or s_ref[1] != 0 or s.op != "Sigmoid" or len(s.inputs) != 1 or \
+                    c.only_consumer(s.name) is not m or _const(g, x_ref) is not None:
+                continue
+            inner = [s]
+            if s.inputs[0] != x_ref:
+                b = g.nodes.get(s.inputs[0][0])
+                if b is None or s.inputs[0][1] != 0 or b.op != "Mul" or len(b.inputs) != 2 or \
+                        c.only_consumer(b.name) is not s:
+                    continue
+                k_ref = _other(b, x_ref)
+                if k_ref is None or k_ref == x_ref or _one_element(g, k_ref, 1.0, 0.0) is None:
+                    continue
+                inner = [b, s]
+            chain = inner + [m]
+            idn = c.only_consumer(m.name)
+            if idn is not None and idn.op == "IdentityN" and idn.inputs and idn.inputs[0] == (m.name, 0) and \
+                    all(r != (m.name, 0) for r in idn.inputs[1:]):
+                readers = c.cons.get(idn.name, [])
+                if not all(oidx == 0 for _n, _p, oidx in readers) or \
+                        any(fn == idn.name and fi != 0 for fn, fi in c.fetch_refs):
+                    continue          # a wrapper whose other outputs are in use is left as it is, swish and all
+                chain.append(idn)
+            _finalize(g, chain, "_Swish", [x_ref], {})
+            c.refresh()
+            break
+
 # ------------------------------------------------------------------ squeeze-and-excite
 class SqueezeExcite:
-    """``x * hard_sigmoid(act1(mean_hw(x) w1 + b1) w2 + b2)`` with the gate
-    broadcast over H and W.  w1 [C][Cr], w2 [Cr][C]: the TF 1x1 filters reshaped
+    """``x * gate(act1(mean_hw(x) w1 + b1) w2 + b2)`` with the gate broadcast
+    over H and W; ``gate`` is "hard_sigmoid" (``_SqueezeExcite``, MobileNetV3) or
+    "sigmoid" (``_SqueezeExciteSigmoid``, EfficientNet: ``torch.sigmoid`` on the
+    reference path, ``scale`` unused).  w1 [C][Cr], w2 [Cr][C]: the TF 1x1 filters reshaped
     [Cin][Cout]; they and the biases stay fp32 on both paths.  On the GPU two
     launches, ``se_gate`` then ``se_scale`` (kernels/se.hip), which use 1/6 for
     the gate's scale; the reference path multiplies by the graph's constant.
@@ -1781,9 +1850,10 @@ class SqueezeExcite:
     gets the original nodes' semantics from torch."""
 
     def __init__(self, w1, b1, w2, b2, act1: str, scale: float, keep_dims: bool, axes, reshape, device, use_hip: bool,
-                 name: str):
+                 name: str, gate: str = "hard_sigmoid"):
         self.c, self.cr = w1.shape
         self.act1 = act1
+        self.gate = gate
         self.scale = float(scale)
         self.keep = keep_dims
         self.axes = tuple(int(a) for a in axes)
@@ -1803,6 +1873,11 @@ class SqueezeExcite:
     def _params(self, dev):
         return (t.to(dev) for t in (self.w1, self.b1, self.w2, self.b2))
 
+    def _gate(self, z):
+        if self.gate == "sigmoid":
+            return torch.sigmoid(z)
+        return torch.clamp(z + 3.0, 0.0, 6.0) * self.scale
+
     def _original(self, x):
         """The matched nodes one by one (Mean, [Reshape], Conv2D + bias, act1,
         Conv2D + bias, hard-sigmoid, Mul) for an x the kernels do not take."""
@@ -1815,8 +1890,7 @@ class SqueezeExcite:
         def conv1x1(t, w):
             return F.conv2d(t.permute(0, 3, 1, 2), w.t().reshape(w.shape[1], w.shape[0], 1, 1)).permute(0, 2, 3, 1)
         h = _ref_act(conv1x1(p, w1) + b1, self.act1)
-        gate = torch.clamp(conv1x1(h, w2) + b2 + 3.0, 0.0, 6.0) * self.scale
-        return xf * gate
+        return xf * self._gate(conv1x1(h, w2) + b2)
 
     def __call__(self, ctx, node, ins):
         x = O.to_torch(ins[0])
@@ -1828,13 +1902,12 @@ class SqueezeExcite:
             H = hip()
             if H.se_gate_supported(x.shape[0], x.shape[1] * x.shape[2], self.c, self.cr) and x.numel() > 0:
                 xb = _to_bf16(x).contiguous()
-                gate = H.se_gate(xb, self.w1, self.b1, self.w2, self.b2, ACT[self.act1], ACT["hard_sigmoid"])
+                gate = H.se_gate(xb, self.w1, self.b1, self.w2, self.b2, ACT[self.act1], ACT[self.gate])
                 return [H.se_scale(xb, gate)]
         w1, b1, w2, b2 = self._params(x.device)
         xf = x.float()
         h = _ref_act(xf.mean(dim=(1, 2)) @ w1 + b1, self.act1)
-        gate = torch.clamp(h @ w2 + b2 + 3.0, 0.0, 6.0) * self.scale
-        y = xf * gate[:, None, None, :]
+        y = xf * self._gate(h @ w2 + b2)[:, None, None, :]
         return [y.to(BF16) if x.dtype == BF16 else y]
 
 
@@ -1861,6 +1934,21 @@ def fuse_squeeze_excite(g, order, fed, fetch_refs, device, opts):
     of the gate chain is read once and not fetched.  Runs after fuse_pools and
     fuse_hard_activations and before fuse_conv, which would otherwise take the
     FCs and keep only bf16 weights."""
+    _fuse_squeeze_excite(g, order, fed, fetch_refs, device, opts, "_HardSigmoid", ("Relu",), "_SqueezeExcite")
+
+
+def fuse_squeeze_excite_sigmoid(g, order, fed, fetch_refs, device, opts):
+    """fuse_squeeze_excite's pattern with a plain ``Sigmoid`` gate and a none /
+    ``Relu`` / ``_Swish`` inner activation -> ``_SqueezeExciteSigmoid(x)``
+    (EfficientNet), never ``_SqueezeExcite``.  Runs after fuse_swish, next to
+    fuse_squeeze_excite."""
+    _fuse_squeeze_excite(g, order, fed, fetch_refs, device, opts, "Sigmoid", ("Relu", "_Swish"),
+                         "_SqueezeExciteSigmoid")
+
+
+def _fuse_squeeze_excite(g, order, fed, fetch_refs, device, opts, gate_op, act1_ops, out_op):
+    """The squeeze-excite pattern gated by ``gate_op`` with an inner activation
+    of ``act1_ops`` (or none) -> ``out_op``."""
     c = _Ctx(g, order, fed, fetch_refs, device, opts)
 
     def up(ref, reader, ops):
@@ -1893,8 +1981,8 @@ def fuse_squeeze_excite(g, order, fed, fetch_refs, device, opts):
         if m is None or m.op != "Mul" or len(m.inputs) != 2:
             continue
         for x_ref, g_ref in ((m.inputs[0], m.inputs[1]), (m.inputs[1], m.inputs[0])):
-            hs = up(g_ref, m, ("_HardSigmoid",))
-            if hs is None or x_ref == g_ref:
+            hs = up(g_ref, m, (gate_op,))
+            if hs is None or x_ref == g_ref or len(hs.inputs) != 1:
                 continue
             f2 = fc(hs.inputs[0], hs)
             if f2 is None:
@@ -1902,9 +1990,9 @@ def fuse_squeeze_excite(g, order, fed, fetch_refs, device, opts):
             nodes2, conv2, w2, b2 = f2
             act1, reader, ref = "none", conv2, conv2.inputs[0]
             chain = [hs] + nodes2
-            relu = up(ref, conv2, ("Relu",))
+            relu = up(ref, conv2, act1_ops)
             if relu is not None:
-                act1, reader, ref = "relu", relu, relu.inputs[0]
+                act1, reader, ref = _CLOSING_ACTS[relu.op], relu, relu.inputs[0]
                 chain.append(relu)
             f1 = fc(ref, reader)
             if f1 is None:
@@ -1932,8 +2020,9 @@ def fuse_squeeze_excite(g, order, fed, fetch_refs, device, opts):
                 continue
             chain.append(pool)
             impl = SqueezeExcite(w1, b1, w2, b2, act1, hs.attr("scale", 1.0 / 6.0), pimpl.keep, pimpl.axes, reshape,
-                                 device, c.use_hip, m.name)
-            _finalize(g, chain[::-1] + [m], "_SqueezeExcite", [x_ref], {"_impl": impl})
+                                 device, c.use_hip, m.name,
+                                 gate="sigmoid" if gate_op == "Sigmoid" else "hard_sigmoid")
+            _finalize(g, chain[::-1] + [m], out_op, [x_ref], {"_impl": impl})
             c.refresh()
             break
 
@@ -2237,7 +2326,8 @@ def fuse_conv_chain(g, order, fed, fetch_refs, device, opts):
 
 def default_passes(options=None):
     from .patterns import bert_passes, late_passes
-    return [fuse_pools, fuse_softmax_argmax, fuse_hard_activations, fuse_squeeze_excite] + bert_passes() + \
+    return [fuse_pools, fuse_softmax_argmax, fuse_hard_activations, fuse_swish, fuse_squeeze_excite,
+            fuse_squeeze_excite_sigmoid] + bert_passes() + \
         [fuse_grouped_conv, fuse_conv, fuse_depthwise, fuse_dual_conv, fuse_post_activation, fuse_stem_pool, fuse_matmul,
          fuse_classifier_head, fuse_dense_softmax, fuse_conv_chain] + late_passes() + \
         [fuse_matmul_layernorm, defer_layernorm, release_weight_sources]

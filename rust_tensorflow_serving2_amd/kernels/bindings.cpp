@@ -141,16 +141,18 @@ const uint16_t* bf16p(const Tensor& t) { return reinterpret_cast<const uint16_t*
 // Hard-swish (code 7) shares all of this: built where ReLU6 is, rejected where
 // ReLU6 is.  relu6_cfg answers for both "igemm-only" activations.  Hard-sigmoid
 // (code 6) is a gate activation of se.hip: no GEMM / conv epilogue takes it.
+// Swish (code 9) is the third igemm-only activation, and sigmoid (code 8) the
+// second gate-only one.
 bool relu6_cfg(int64_t cfg) {
   return config_of(cfg) != nullptr && config_of(cfg)->family == tfsk::TileFamily::kIGemm;
 }
 void need_act(int64_t act, int64_t cfg, const char* op) {
-  TORCH_CHECK((act >= tfsk::kActNone && act <= tfsk::kActRelu6) || act == tfsk::kActHardSwish, op,
-              ": unknown activation code ", act);
-  const bool igemm_only = act == tfsk::kActRelu6 || act == tfsk::kActHardSwish;
+  TORCH_CHECK((act >= tfsk::kActNone && act <= tfsk::kActRelu6) || act == tfsk::kActHardSwish ||
+              act == tfsk::kActSwish, op, ": unknown activation code ", act);
+  const bool igemm_only = act == tfsk::kActRelu6 || act == tfsk::kActHardSwish || act == tfsk::kActSwish;
   TORCH_CHECK(!igemm_only || config_of(cfg) == nullptr || relu6_cfg(cfg), op, ": activation ",
-              act == tfsk::kActRelu6 ? "relu6" : "hard_swish", " is built into the igemm kernels only (tile config ",
-              cfg, " is not one)");
+              act == tfsk::kActRelu6 ? "relu6" : act == tfsk::kActHardSwish ? "hard_swish" : "swish",
+              " is built into the igemm kernels only (tile config ", cfg, " is not one)");
 }
 void need_post_act(int64_t act, const char* op) {
   TORCH_CHECK(act == tfsk::kActNone || act == tfsk::kActRelu, op, ": the post activation is none (0) or relu (1), got ",
@@ -360,7 +362,7 @@ std::vector<Tensor> linear_lnx(const Tensor& x, const Tensor& w, const c10::opti
                                const c10::optional<Tensor>& r_st, const c10::optional<Tensor>& r_gamma,
                                const c10::optional<Tensor>& r_beta, double r_eps, bool stats) {
   TORCH_CHECK(act >= tfsk::kActNone && act <= tfsk::kActTanh, "linear_lnx: unknown activation code ", act,
-              " (the deferred-LayerNorm epilogue has no relu6 and no hard_swish)");
+              " (the deferred-LayerNorm epilogue has no relu6, no hard_swish and no swish)");
   need(x, at::kBFloat16, "x");
   need(w, at::kBFloat16, "w");
   c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
@@ -498,8 +500,9 @@ Tensor maxpool(const Tensor& x, int64_t KH, int64_t KW, int64_t SH, int64_t SW, 
 Tensor dwconv2d(const Tensor& x, const Tensor& w, const Tensor& bias, int64_t KH, int64_t KW, int64_t SH, int64_t SW,
                 int64_t PT, int64_t PL, int64_t Ho, int64_t Wo, int64_t act, const c10::optional<Tensor>& out,
                 int64_t strip) {
-  TORCH_CHECK(act == tfsk::kActNone || act == tfsk::kActRelu || act == tfsk::kActRelu6 || act == tfsk::kActHardSwish,
-              "dwconv2d: the activation is none (0), relu (1), relu6 (5) or hard_swish (7), got ", act);
+  TORCH_CHECK(act == tfsk::kActNone || act == tfsk::kActRelu || act == tfsk::kActRelu6 ||
+              act == tfsk::kActHardSwish || act == tfsk::kActSwish,
+              "dwconv2d: the activation is none (0), relu (1), relu6 (5), hard_swish (7) or swish (9), got ", act);
   need(x, at::kBFloat16, "x");
   need(w, at::kFloat, "w");
   need(bias, at::kFloat, "bias");
@@ -514,10 +517,15 @@ Tensor dwconv2d(const Tensor& x, const Tensor& w, const Tensor& bias, int64_t KH
   TORCH_CHECK(w.numel() == KH * KW * C, "dwconv2d: w must be [KH*KW][C] (channel multiplier 1)");
   TORCH_CHECK(bias.numel() == C, "dwconv2d: bias must have C entries");
   TORCH_CHECK(w.device() == x.device() && bias.device() == x.device(), "dwconv2d: tensors on different devices");
-  TORCH_CHECK(strip == 0 || strip == tfsk::kDwStripShort || strip == tfsk::kDwStripTall, "dwconv2d: strip must be 0, ",
-              tfsk::kDwStripShort, " or ", tfsk::kDwStripTall);
+  const bool five = KH == 5 && KW == 5 && SH == SW && (SH == 1 || SH == 2);
+  TORCH_CHECK(strip == 0 || strip == tfsk::kDwStripShort || strip == tfsk::kDwStripTall ||
+              (five && strip == tfsk::kDwStrip5Tall), "dwconv2d: strip must be 0, ", tfsk::kDwStripShort, " or ",
+              tfsk::kDwStripTall, " (or, for a 5 x 5 filter with equal strides 1 or 2, ", tfsk::kDwStrip5Tall,
+              "), got ", strip);
   TORCH_CHECK(x.numel() * 2 < 0x7ffffff0LL && N * Ho * Wo * C * 2 < 0x7ffffff0LL, "dwconv2d operands must be < 2 GiB");
   TORCH_CHECK(Wo * (C / 8) <= 65535LL * 256, "dwconv2d: output rows of more than 16 M chunks");
+  TORCH_CHECK(!(five && strip != 0 && strip != tfsk::kDwStripTall) || Wo * (C / 4) <= 65535LL * 256,
+              "dwconv2d: output rows of more than 8 M half chunks (5 x 5 strips)");
   c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
   Tensor y = out.has_value() ? *out : torch::empty({N, Ho, Wo, C}, x.options());
   need(y, at::kBFloat16, "out");
@@ -573,8 +581,10 @@ Tensor gconv2d(const Tensor& x, const Tensor& w, const Tensor& bias, int64_t cg,
 // gate_act(act1(mean_hw(x) w1 + b1) w2 + b2).
 Tensor se_gate(const Tensor& x, const Tensor& w1, const Tensor& b1, const Tensor& w2, const Tensor& b2, int64_t act1,
                int64_t gate_act, const c10::optional<Tensor>& out) {
-  TORCH_CHECK(act1 == tfsk::kActNone || act1 == tfsk::kActRelu, "se_gate: act1 is none (0) or relu (1), got ", act1);
-  TORCH_CHECK(gate_act == tfsk::kActHardSigmoid, "se_gate: gate_act is hard_sigmoid (6), got ", gate_act);
+  TORCH_CHECK(act1 == tfsk::kActNone || act1 == tfsk::kActRelu || act1 == tfsk::kActSwish,
+              "se_gate: act1 is none (0), relu (1) or swish (9), got ", act1);
+  TORCH_CHECK(gate_act == tfsk::kActHardSigmoid || gate_act == tfsk::kActSigmoid,
+              "se_gate: gate_act is hard_sigmoid (6) or sigmoid (8), got ", gate_act);
   need(x, at::kBFloat16, "x");
   need(w1, at::kFloat, "w1");
   need(b1, at::kFloat, "b1");
@@ -1068,6 +1078,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
                            int64_t sw) {
     return tfsk::dwconv_strip(int(n), int(ho), int(wo), int(c), int(kh), int(kw), int(sh), int(sw));
   }, "output rows per thread dwconv2d picks by itself (0: the generic kernel, which has no strips)");
+  m.def("dwconv_forms", [](int64_t n, int64_t ho, int64_t wo, int64_t c, int64_t kh, int64_t kw, int64_t sh,
+                           int64_t sw) {
+    int forms[tfsk::kDwMaxForms];
+    const int k = tfsk::dwconv_forms(int(n), int(ho), int(wo), int(c), int(kh), int(kw), int(sh), int(sw), forms);
+    return std::vector<int64_t>(forms, forms + k);
+  }, "the strip values dwconv2d takes for the shape: [0], [0, 2, 8] (3 x 3 strips) or [0, 2, 4] (5 x 5 strips)");
   m.def("gconv2d", &gconv2d, "grouped 3x3 conv on MFMA: act(conv(x, w packed bf16) + bias), NHWC bf16", py::arg("x"),
         py::arg("w"), py::arg("bias"), py::arg("cg"), py::arg("sh"), py::arg("pt"), py::arg("pl"), py::arg("ho"),
         py::arg("wo"), py::arg("act") = 0, py::arg("out") = py::none(), py::arg("cg_out") = -1, py::arg("sw") = -1,

@@ -20,7 +20,11 @@ enum Act : int { kActNone = 0, kActRelu = 1, kActGeluTanh = 2, kActGeluErf = 3, 
                  // hard-sigmoid clamp(x + 3, 0, 6) / 6: a gate activation (se.hip), no GEMM / conv epilogue
                  kActHardSigmoid = 6,
                  // hard-swish x * hard_sigmoid(x): dwconv.hip, igemm.hip and the split-K reduce
-                 kActHardSwish = 7 };
+                 kActHardSwish = 7,
+                 // sigmoid 1 / (1 + exp(-x)): a gate activation (se.hip), no GEMM / conv epilogue
+                 kActSigmoid = 8,
+                 // swish (SiLU) x * sigmoid(x): dwconv.hip, igemm.hip, the split-K reduce and se.hip's act1
+                 kActSwish = 9 };
 
 __device__ __forceinline__ float bf16_to_f32(bf16_t v) {
   return __uint_as_float(uint32_t(v) << 16);
@@ -54,6 +58,12 @@ __device__ __forceinline__ float gelu_tanh(float x) {
 // clamp(x + 3, 0, 6) * (1/6): one add, two clamps, one product
 __device__ __forceinline__ float hard_sigmoid(float x) { return fminf(fmaxf(x + 3.f, 0.f), 6.f) * (1.f / 6.f); }
 
+// 1 / (1 + exp(-x)) as rcp(1 + exp2(-log2(e) x)): one product, v_exp_f32, one add, v_rcp_f32 (sigm2's
+// idiom with the constant folded).  Limits: x -> -inf gives rcp(inf) = 0, x -> +inf gives rcp(1) = 1.
+__device__ __forceinline__ float sigmoid(float x) {
+  return __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(x * -1.4426950408889634f));
+}
+
 __device__ __forceinline__ float apply_act(float x, int act) {
   switch (act) {
     case kActRelu: return x > 0.f ? x : 0.f;
@@ -63,6 +73,8 @@ __device__ __forceinline__ float apply_act(float x, int act) {
     case kActRelu6: return fminf(fmaxf(x, 0.f), 6.f);
     case kActHardSigmoid: return hard_sigmoid(x);
     case kActHardSwish: return x * hard_sigmoid(x);
+    case kActSigmoid: return sigmoid(x);
+    case kActSwish: return x * sigmoid(x);
     default: return x;
   }
 }
@@ -85,6 +97,10 @@ __device__ __forceinline__ float act_fn(float x) {
     return hard_sigmoid(x);
   } else if constexpr (ACT == kActHardSwish) {
     return x * hard_sigmoid(x);
+  } else if constexpr (ACT == kActSigmoid) {
+    return sigmoid(x);
+  } else if constexpr (ACT == kActSwish) {
+    return x * sigmoid(x);
   } else {
     return x;
   }

@@ -20,11 +20,11 @@ namespace gemm {
 // Runtime activation code -> compile-time tag: f(std::integral_constant<int, ACT>{}).
 // WITH_ERF = false: erf GELU takes the default (none) -- the callers that
 // exclude erf beforehand do not pay for its expansion.
-// WITH_RELU6: the kernel also builds the ReLU6 and hard-swish epilogues (the
-// "igemm-only" activations).  igemm only: it takes every shape, so a relu6 or
-// hard-swish conv always has a kernel.  bgemm and halo keep the four-case
-// switch (their code is unchanged by either), and the bindings reject both on
-// their configs as they do on cgemm's.
+// WITH_RELU6: the kernel also builds the ReLU6, hard-swish and swish epilogues
+// (the "igemm-only" activations).  igemm only: it takes every shape, so a
+// relu6, hard-swish or swish conv always has a kernel.  bgemm and halo keep the
+// four-case switch (their code is unchanged by any of them), and the bindings
+// reject all three on their configs as they do on cgemm's.
 template <bool WITH_ERF = true, bool WITH_RELU6 = false, class F>
 __device__ __forceinline__ void dispatch_act(int act, F&& f) {
   if constexpr (WITH_RELU6) {
@@ -34,6 +34,10 @@ __device__ __forceinline__ void dispatch_act(int act, F&& f) {
     }
     if (act == kActHardSwish) {
       f(std::integral_constant<int, kActHardSwish>{});
+      return;
+    }
+    if (act == kActSwish) {
+      f(std::integral_constant<int, kActSwish>{});
       return;
     }
   }

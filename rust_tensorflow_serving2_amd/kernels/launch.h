@@ -166,13 +166,20 @@ hipError_t maxpool_nhwc_launch(const uint16_t* x, uint16_t* y, int N, int H, int
                                int act = 0);
 // NHWC bf16 depthwise conv, channel multiplier 1 (dwconv.hip): x [N][H][W][C]
 // (C % 8 == 0), w [KH*KW][C] f32, bias [C] f32 -> y [N][Ho][Wo][C] bf16 =
-// act(conv + bias), act in {kActNone, kActRelu, kActRelu6, kActHardSwish}; KH, KW <= 7,
+// act(conv + bias), act in {kActNone, kActRelu, kActRelu6, kActHardSwish, kActSwish}; KH, KW <= 7,
 // explicit top / left padding, Ho / Wo from the caller (taps outside the image
 // read zero).  3x3 with stride 1 or 2 runs the strip kernels, `strip` output
 // rows per thread (kDwStripShort, kDwStripTall, or 0: dwconv_strip's rule);
-// anything else the generic kernel.  Operands must be < 2 GiB.
+// 5x5 with stride 1 or 2 runs its strip kernel for strip kDwStrip5Short or
+// kDwStrip5Tall (bit-equal to the generic kernel) and the generic kernel for
+// any other accepted value; anything else the generic kernel.  dwconv_forms
+// writes the strip values worth timing for a shape (0 first, at most
+// kDwMaxForms) and returns their count.  Operands must be < 2 GiB.
 constexpr int kDwStripShort = 2, kDwStripTall = 8;
+constexpr int kDwStrip5Short = 2, kDwStrip5Tall = 4;
+constexpr int kDwMaxForms = 3;
 int dwconv_strip(int N, int Ho, int Wo, int C, int KH, int KW, int SH, int SW, int strip = 0);
+int dwconv_forms(int N, int Ho, int Wo, int C, int KH, int KW, int SH, int SW, int* forms);
 hipError_t dwconv_nhwc_launch(const uint16_t* x, const float* w, const float* bias, uint16_t* y, int N, int H, int W,
                               int C, int KH, int KW, int SH, int SW, int PT, int PL, int Ho, int Wo, int act,
                               int strip, hipStream_t stream);
@@ -199,7 +206,7 @@ hipError_t gconv_nhwc_launch(const uint16_t* x, const uint16_t* w, const float* 
 // gate [B][C] f32 = gate_act(act1(mean_hw(x) w1 + b1) w2 + b2), all in fp32.
 // The weights are the TF 1x1 filters as they are, row-major [Cin][Cout] f32:
 // w1 [C][Cr], b1 [Cr], w2 [Cr][C], b2 [C], 1 <= Cr <= kSeMaxCr.  act1 is
-// kActNone or kActRelu, gate_act kActHardSigmoid.  One workgroup per image;
+// kActNone, kActRelu or kActSwish, gate_act kActHardSigmoid or kActSigmoid.  One workgroup per image;
 // x must be < 2 GiB.  se_gate_supported: the shape limits alone.
 // se_scale: y [B][HW][C] bf16 = bf16(x * gate[b][c]) (C % 8 == 0, x < 2 GiB).
 constexpr int kSeMaxC = 2048, kSeMaxCr = 512;

@@ -1,6 +1,6 @@
 // Squeeze-and-excite (gfx950), NHWC bf16 activation, fp32 weights and gate:
-//   se_gate:  gate[b][c] = gate_act(b2[c] + sum_r h[b][r] w2[r][c]),
-//             h[b][r] = act1(b1[r] + sum_c p[b][c] w1[c][r]),
+//   se_gate:  gate[b][c] = gate_act(b2[c] + sum_r h[b][r] w2[r][c]),        (hard-sigmoid or sigmoid)
+//             h[b][r] = act1(b1[r] + sum_c p[b][c] w1[c][r]),               (none, ReLU or swish)
 //             p[b][c] = (1 / HW) sum_{h,w} x[b][h][w][c]           (fp32 throughout)
 //   se_scale: y[b][h][w][c] = bf16(x[b][h][w][c] * gate[b][c])
 // Two launches per block; no atomics anywhere, every sum has a fixed order, so
@@ -223,8 +223,8 @@ bool se_gate_supported(long B, long HW, long C, long Cr) {
 hipError_t se_gate_launch(const uint16_t* x, const float* w1, const float* b1, const float* w2, const float* b2,
                           float* gate, int B, int HW, int C, int Cr, int act1, int gate_act, hipStream_t s) {
   if (!se_gate_supported(B, HW, C, Cr)) return hipErrorInvalidValue;
-  if (act1 != kActNone && act1 != kActRelu) return hipErrorInvalidValue;
-  if (gate_act != kActHardSigmoid) return hipErrorInvalidValue;
+  if (act1 != kActNone && act1 != kActRelu && act1 != kActSwish) return hipErrorInvalidValue;
+  if (gate_act != kActHardSigmoid && gate_act != kActSigmoid) return hipErrorInvalidValue;
   if (B == 0) return hipSuccess;
   const SeGateArgs a{x, w1, b1, w2, b2, gate, B, HW, C, Cr, act1, gate_act, 1.f / float(HW)};
   hipLaunchKernelGGL(se_gate_kernel, dim3(unsigned(B)), dim3(kThreads), 0, s, a);

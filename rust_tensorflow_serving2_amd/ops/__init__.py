@@ -52,10 +52,10 @@ def available() -> bool:
 
 
 ACT = {"none": 0, "relu": 1, "gelu_tanh": 2, "gelu_erf": 3, "tanh": 4, "relu6": 5,
-       "hard_sigmoid": 6, "hard_swish": 7}   # kernels/common.h Act
+       "hard_sigmoid": 6, "hard_swish": 7, "sigmoid": 8, "swish": 9}   # kernels/common.h Act
 # the activations only the igemm kernels (and the split-K reduce) implement: their launches
 # pass relu6=True (or its alias igemm_act=True) to candidates / tuned_config
-IGEMM_ONLY_ACTS = ("relu6", "hard_swish")
+IGEMM_ONLY_ACTS = ("relu6", "hard_swish", "swish")
 
 # ------------------------------------------------------------------ autotune
 _TUNED: Dict[Tuple, int] = {}
@@ -206,7 +206,7 @@ def candidates(M: int, N: int, K: int, dma: bool = True, aligned64: bool = False
     stride-1 conv with C % 64 == 0, so the halo-tiled configs apply too —
     their split-K granule is a 64-channel chunk of 9 taps; ``stem``: the
     padded RGBA stem operand, which the 32-deep and persistent builds do not
-    take; ``relu6``: the launch's activation is ReLU6 or hard-swish, which only
+    take; ``relu6``: the launch's activation is ReLU6, hard-swish or swish, which only
     the igemm kernels implement; ``igemm_act`` is an alias of it)."""
     relu6 = relu6 or igemm_act
     nk = -(-K // 64)
@@ -235,7 +235,7 @@ def candidates(M: int, N: int, K: int, dma: bool = True, aligned64: bool = False
         if cgemm_only and cfg not in CGEMM:
             continue
         if relu6 and cfg in CGEMM:
-            continue   # ReLU6 / hard-swish are igemm epilogues only (the bindings reject them elsewhere)
+            continue   # ReLU6 / hard-swish / swish are igemm epilogues only (the bindings reject them elsewhere)
         if cfg in BGEMM and (stem or ln or not PINGPONG):
             continue   # dense operands, plain epilogues only
         if ln and (cfg not in CGEMM or bn % 32):

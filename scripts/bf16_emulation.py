@@ -1,6 +1,7 @@
 #!/usr/bin/env python
 """What does bf16 storage alone cost a MobileNet (or, with --family resnext, a
-ResNeXt-50 32x4d) end to end?  CPU only.
+ResNeXt-50 32x4d; with --family efficientnet, an EfficientNet-B0) end to end?
+CPU only.
 
 Exports a random-init model, runs the fp32 interpreter, and runs the fused
 CPU program a second time with the conv weights rounded to bf16 and the output of
@@ -17,10 +18,12 @@ program stores -- with everything else in fp32.  Prints, per input seed:
   of the rounding errors, as another summation order would give.
 
 `--gated-gain` / `--expand-gain` override models/mobilenet.py's init gains
-(V3_GATED_PROJECT_GAIN / V3_EXPAND_GAIN) for the exported model.
+(V3_GATED_PROJECT_GAIN / V3_EXPAND_GAIN) for the exported model, or, with
+--family efficientnet, models/efficientnet.py's GATED_PROJECT_GAIN / EXPAND_GAIN.
 
     python scripts/bf16_emulation.py --version v3_small --seeds 0 1 2 3 --trials 3
     python scripts/bf16_emulation.py --family resnext --seeds 3 4 --trials 1
+    python scripts/bf16_emulation.py --family efficientnet --seeds 0 1 2 --trials 3
 """
 import argparse
 import os
@@ -35,7 +38,7 @@ from rust_tensorflow_serving2_amd.models import mobilenet  # noqa: E402
 from rust_tensorflow_serving2_amd.server.servable import Servable, ServableOptions  # noqa: E402
 
 OUTS = ["classes", "probabilities"]
-ROUNDED = ("_FusedConv2D", "_FusedGroupedConv2D", "_FusedDepthwiseConv2D", "_SqueezeExcite")
+ROUNDED = ("_FusedConv2D", "_FusedGroupedConv2D", "_FusedDepthwiseConv2D", "_SqueezeExcite", "_SqueezeExciteSigmoid")
 
 
 def bf16(t):
@@ -72,9 +75,10 @@ def emulate(program, trial):
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
-    ap.add_argument("--family", default="mobilenet", choices=["mobilenet", "resnext"],
-                    help="resnext: ResNeXt-50 32x4d at full width (tests/test_resnext_gpu.py's model); --version and "
-                         "the gains are MobileNet's")
+    ap.add_argument("--family", default="mobilenet", choices=["mobilenet", "resnext", "efficientnet"],
+                    help="resnext: ResNeXt-50 32x4d at full width (tests/test_resnext_gpu.py's model); efficientnet: "
+                         "EfficientNet-B0 at full width (tests/test_efficientnet_gpu.py's model); --version is "
+                         "MobileNet's")
     ap.add_argument("--version", default="v3_small", choices=mobilenet.VERSIONS)
     ap.add_argument("--image-size", type=int, default=64)
     ap.add_argument("--model-seed", type=int, default=3)
@@ -88,13 +92,23 @@ def main():
         mobilenet.V3_GATED_PROJECT_GAIN = dict(mobilenet.V3_GATED_PROJECT_GAIN, **{a.version: a.gated_gain})
     if a.expand_gain is not None:
         mobilenet.V3_EXPAND_GAIN = dict(mobilenet.V3_EXPAND_GAIN, **{a.version: a.expand_gain})
-    if a.family == "resnext":
+    if a.family == "efficientnet":
+        from rust_tensorflow_serving2_amd.models import efficientnet
+        a.version = "efficientnet_b0"
+        if a.gated_gain is not None:
+            efficientnet.GATED_PROJECT_GAIN = a.gated_gain
+        if a.expand_gain is not None:
+            efficientnet.EXPAND_GAIN = a.expand_gain
+        print(a.version, "gated project gain", efficientnet.GATED_PROJECT_GAIN, "expand gain", efficientnet.EXPAND_GAIN)
+    elif a.family == "resnext":
         a.version = "resnext50"
     elif a.version.startswith("v3"):
         print(a.version, "gated project gain", mobilenet.V3_GATED_PROJECT_GAIN[a.version], "expand gain",
               mobilenet.V3_EXPAND_GAIN[a.version])
     path = os.path.join(tempfile.mkdtemp(), "1")
-    if a.family == "resnext":
+    if a.family == "efficientnet":
+        efficientnet.export(path, image_size=a.image_size, seed=a.model_seed)
+    elif a.family == "resnext":
         from rust_tensorflow_serving2_amd.models import resnet
         resnet.export(path, groups=32, width_per_group=4, image_size=a.image_size, seed=a.model_seed)
     else:

@@ -18,7 +18,11 @@ records the start event and issues the launch):
 
 Prints one table row per shape and, with --json, one JSON line per shape.
 
-    python scripts/dwconv_bench.py [--batch 32] [--reps 21] [--json]
+``--k5`` times, instead, the distinct 5x5 depthwise shapes of EfficientNet-B0 and
+MobileNetV3-Large (224 x 224) with a swish epilogue: the generic kernel, the 5x5
+strip kernel at both heights (2 and 4 output rows per thread) and the copy floor.
+
+    python scripts/dwconv_bench.py [--batch 32] [--reps 21] [--json] [--k5]
 """
 import argparse
 import json
@@ -48,6 +52,64 @@ def mobilenet_dw_shapes():
     return shapes
 
 
+def k5_dw_shapes():
+    """Distinct (H, W, C, stride, padding) of the 5x5 depthwise layers of
+    EfficientNet-B0 and MobileNetV3-Large, padding as the exporters write it."""
+    from rust_tensorflow_serving2_amd.models import efficientnet, mobilenet
+    shapes = {}
+    size = 112
+    for k, repeats, fin, fout, ratio, first in efficientnet.BLOCKS:
+        for r in range(repeats):
+            stride, cin = (first, fin) if r == 0 else (1, fout)
+            if k == 5:
+                shapes.setdefault((size, size, cin * ratio, stride, "SAME" if stride == 1 else "PAD_VALID"), []).append("b0")
+            size = -(-size // stride)
+    size = 112
+    for k, exp, _out, _se, _act, stride in mobilenet.V3_LARGE:
+        if k == 5:
+            shapes.setdefault((size, size, exp, stride, "SAME" if stride == 1 else "PAD_VALID"), []).append("v3l")
+        size = -(-size // stride)
+    return shapes
+
+
+def bench_k5(args, H, ops, O, dev, flush):
+    n = args.batch
+    print(f"{'H x W x C':>16} {'s':>2} {'pad':>9} {'models':>6} {'generic us':>10} {'strip2 us':>9} {'strip4 us':>9} "
+          f"{'copy us':>8} {'generic/best':>12} {'best/copy':>9}")
+    for (h, w, c, s, padding), users in sorted(k5_dw_shapes().items(), key=lambda kv: (-kv[0][0], kv[0][2])):
+        g = torch.Generator().manual_seed(h * 1000 + c)
+        x = torch.randn(n, h, w, c, generator=g).to(torch.bfloat16).to(dev)
+        w25 = (torch.randn(25, c, generator=g) / 5).to(dev)
+        b = torch.randn(c, generator=g).to(dev)
+        if padding == "SAME":
+            pads = O.tf_same_pads(h, 5, s) + O.tf_same_pads(w, 5, s)
+        else:                                           # Keras correct_pad in front of a VALID conv
+            pads = (2 - (1 - h % 2), 2, 2 - (1 - w % 2), 2)
+        ho, wo = (h + pads[0] + pads[1] - 5) // s + 1, (w + pads[2] + pads[3] - 5) // s + 1
+        out = torch.empty(n, ho, wo, c, dtype=torch.bfloat16, device=dev)
+        forms = H.dwconv_forms(n, ho, wo, c, 5, 5, s, s)
+        assert forms == [0, 2, 4], forms
+        outs = {}
+        t = {}
+        for strip in forms:
+            t[strip] = timed(lambda strip=strip: H.dwconv2d(x, w25, b, 5, 5, s, s, pads[0], pads[2], ho, wo,
+                                                            ops.ACT["swish"], out, strip), flush, args.reps)
+            outs[strip] = out.clone()
+        assert all(torch.equal(outs[0].view(torch.int16), outs[f].view(torch.int16)) for f in forms)   # bit-equal forms
+        nbytes = (x.numel() + out.numel()) * 2           # what the op reads + writes
+        src = torch.empty(nbytes // 2, dtype=torch.uint8, device=dev)
+        dst = torch.empty_like(src)
+        copy = timed(lambda: dst.copy_(src), flush, args.reps)
+        best = min(t, key=t.get)
+        row = {"n": n, "h": h, "w": w, "c": c, "k": 5, "stride": s, "padding": padding,
+               "models": "+".join(sorted(set(users))), "generic_us": round(t[0], 2), "strip2_us": round(t[2], 2),
+               "strip4_us": round(t[4], 2), "best": best, "copy_us": round(copy, 2), "bytes": nbytes}
+        print(f"{f'{h}x{w}x{c}':>16} {s:>2} {padding:>9} {row['models']:>6} {t[0]:10.1f} {t[2]:9.1f} {t[4]:9.1f} "
+              f"{copy:8.1f} {t[0] / t[best]:12.2f} {t[best] / copy:9.2f}", flush=True)
+        if args.json:
+            print(json.dumps(row), flush=True)
+
+
 def timed(fn, flush, reps):
     from rust_tensorflow_serving2_amd import ops
     fn()
@@ -71,6 +133,8 @@ def main():
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--reps", type=int, default=21)
     ap.add_argument("--json", action="store_true")
+    ap.add_argument("--k5", action="store_true", help="the 5x5 shapes of EfficientNet-B0 and MobileNetV3-Large: generic "
+                                                      "kernel vs both strip heights vs the copy floor")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("dwconv_bench needs a GPU: a timing taken anywhere else says nothing")
@@ -80,6 +144,8 @@ def main():
     H = ops.hip()
     dev = torch.device("cuda:0")
     flush = ops._flush_buffer()
+    if args.k5:
+        return bench_k5(args, H, ops, O, dev, flush)
     n = args.batch
     print(f"{'H x W x C':>16} {'s':>2} {'pad':>9} {'models':>6} {'new us':>8} {'strip':>5} {'parent us':>10} "
           f"{'copy us':>8} {'parent/new':>10} {'new/copy':>8} {'GB/s':>7}")

@@ -5,7 +5,7 @@ The reference downloads ``resnet_v2_fp32_savedmodel_NHWC`` and copies version
 Offline, we write random-init SavedModels of the same architectures in the
 same ``<root>/<name>/<version>/`` layout:
 
-    python serving/make_models.py --root serving/models [--models resnet,resnet_v2,resnext50,mobilenet,mobilenet_v2,mobilenet_v3_large,mobilenet_v3_small,bert,half_plus_two]
+    python serving/make_models.py --root serving/models [--models resnet,resnet_v2,resnext50,mobilenet,mobilenet_v2,mobilenet_v3_large,mobilenet_v3_small,efficientnet_b0,bert,half_plus_two]
 
 * ``resnet``        ResNet-50 v1.5 (NHWC, alias "input", outputs classes/probabilities)
 * ``resnet_v2``     ResNet-50 v2 pre-activation (the fetch.sh model's architecture)
@@ -13,6 +13,7 @@ same ``<root>/<name>/<version>/`` layout:
 * ``mobilenet``     MobileNet V1 1.0 224 (slim layout: SAME depthwise convs, ReLU6)
 * ``mobilenet_v2``  MobileNet V2 1.0 224 (Keras layout: Pad + VALID on stride 2, linear bottlenecks)
 * ``mobilenet_v3_large`` / ``mobilenet_v3_small``  MobileNetV3 1.0 224 (Keras layout: hard-swish, squeeze-excite)
+* ``efficientnet_b0``  EfficientNet-B0 224 (Keras layout: swish, sigmoid-gated squeeze-excite, 5x5 depthwise convs)
 * ``bert``          BERT-base seq 128 (input_ids / input_mask / segment_ids)
 * ``half_plus_two`` TF Serving's canonical test model
 
@@ -49,6 +50,9 @@ def main(argv=None):
             from rust_tensorflow_serving2_amd.models import mobilenet
             version = {"mobilenet": "v1", "mobilenet_v2": "v2"}.get(m, m[len("mobilenet_"):])
             mobilenet.export(out, version=version, seed=args.seed)
+        elif m == "efficientnet_b0":
+            from rust_tensorflow_serving2_amd.models import efficientnet
+            efficientnet.export(out, seed=args.seed)
         elif m == "bert":
             from rust_tensorflow_serving2_amd.models import bert
             bert.export(out, bert.BertConfig(), seed=args.seed)
