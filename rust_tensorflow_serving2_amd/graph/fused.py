@@ -23,6 +23,12 @@ a single consumer and is not fetched):
   => ``_FusedDepthwiseConv2D`` (channel multiplier 1): BN folded into the fp32
   filter, one ``dwconv2d`` launch (kernels/dwconv.hip).  ``Relu6`` also fuses
   into ``_FusedConv2D`` (MobileNet's pointwise convs).
+* ``_LayerNorm(_FusedDepthwiseConv2D(x))`` with a 7x7 / stride-1 depthwise op without
+  activation => ``_FusedDepthwiseLN`` (ConvNeXt): one ``dwconv_ln`` launch
+  (kernels/dwln.hip), the conv result in fp32 up to the normalised output's one
+  rounding.  A tanh / erf GELU subgraph closes a ``_FusedConv2D`` chain like a
+  one-node activation (after the residual add), and ConvNeXt's layer scale and
+  shortcut are the chain's ``Mul`` by a ``[C]`` constant and residual ``AddV2``.
 * ``[Pad] -> Conv2D -> [BiasAdd] -> [FusedBatchNorm*] -> [Relu]`` whose input has a
   known multiple of the filter's in-depth channels (a grouped conv: ResNeXt)
   => ``_FusedGroupedConv2D``: BN folded, one ``gconv2d`` launch (kernels/gconv.hip)
@@ -392,6 +398,56 @@ class FusedDepthwiseConv:
         key = ("dwconv", tuple(x.shape), self.kh, self.kw, self.sh, self.sw, pt, pl, ho, wo, self.act)
         pick = tuned_choice(key, {2: lambda: run(2), 8: lambda: run(8)}, default=auto)
         return [run(pick)]
+
+
+class FusedDepthwiseLN:
+    """``_LayerNorm(_FusedDepthwiseConv2D(x))`` for a 7x7 / stride-1 depthwise
+    conv without activation: the opening of a ConvNeXt block as one launch
+    (kernels/dwln.hip), the conv result in fp32 up to the one rounding of the
+    normalised output.  It owns the two ops it replaces (``dw``, ``ln``: their
+    weights are its weights) and runs them as they were for an input that is
+    not NHWC with C channels, for a shape the kernel does not take, and under
+    ``TFSERVE_DWLN=0`` (A/B only)."""
+
+    children = ("dw", "ln")             # placement.weight_refs
+
+    def __init__(self, dw: "FusedDepthwiseConv", ln, use_hip: bool, name: str):
+        self.dw, self.ln = dw, ln
+        self.c = dw.c
+        self.eps = ln.eps
+        self.use_hip = use_hip
+        self.name = name
+
+    @staticmethod
+    def shape_ok(dw: "FusedDepthwiseConv") -> bool:
+        """What kernels/dwln.hip takes, the channel count aside."""
+        return dw.kh == 7 and dw.kw == 7 and dw.sh == 1 and dw.sw == 1 and dw.act == "none"
+
+    def _pair(self, ctx, node, x):
+        return self.ln(ctx, node, self.dw(ctx, node, [x]))
+
+    def __call__(self, ctx, node, ins):
+        x = O.to_torch(ins[0])
+        if x.dim() != 4 or x.shape[3] != self.c:
+            return self._pair(ctx, node, x)
+        dw = self.dw
+        pt, pb, pl, pr = dw.pads_for(x.shape[1], x.shape[2])
+        n, h, w, _ = x.shape
+        ho, wo = h + pt + pb - 6, w + pl + pr - 6
+        gamma, beta = self.ln.params(self.c)
+        if not self.use_hip:
+            wt = dw.w.to(x.device).permute(2, 0, 1).reshape(self.c, 1, 7, 7)
+            y = F.conv2d(F.pad(x.float().permute(0, 3, 1, 2), [pl, pr, pt, pb]), wt, groups=self.c)
+            y = y.permute(0, 2, 3, 1) + dw.b.to(x.device)
+            return [F.layer_norm(y, (self.c,), gamma.to(x.device), beta.to(x.device), self.eps).contiguous()]
+        from ..ops import hip
+        H = hip()
+        if (os.environ.get("TFSERVE_DWLN", "1") == "0" or not x.is_cuda or ho < 1 or wo < 1 or
+                not H.dwconv_ln_supported(n, ho, wo, self.c, 7, 7, 1, 1)):
+            return self._pair(ctx, node, x)
+        x = _to_bf16(x).contiguous()
+        out = torch.empty((n, ho, wo, self.c), device=x.device, dtype=BF16)
+        return [H.dwconv_ln(x, dw.w, dw.b, gamma, beta, self.eps, pt, pl, ho, wo, out)]
 
 
 def _grouped_conv_torch(x: torch.Tensor, w_hwio: torch.Tensor, bias: torch.Tensor, strides, pads, groups: int):
@@ -1001,7 +1057,7 @@ def _impl_op(ctx, node, ins):
     return node.attrs["_impl"](ctx, node, ins)
 
 
-for _op in ("_FusedConv2D", "_FusedDepthwiseConv2D", "_FusedGroupedConv2D", "_FusedDualConv", "_FusedMatMul", "_GlobalAvgPool", "_MaxPool",
+for _op in ("_FusedConv2D", "_FusedDepthwiseConv2D", "_FusedDepthwiseLN", "_FusedGroupedConv2D", "_FusedDualConv", "_FusedMatMul", "_GlobalAvgPool", "_MaxPool",
             "_SqueezeExcite", "_SqueezeExciteSigmoid",
             "_SoftmaxArgMax", "_LayerNorm",
             "_FusedQKV", "_Attention", "_EmbeddingLN", "_KeyMaskAdder", "_DenseSoftmax"):
@@ -1599,7 +1655,14 @@ def fuse_conv(g, order, fed, fetch_refs, device, opts):
                 chain.append(nxt)
                 cur = nxt
                 nxt = c.only_consumer(cur.name)
-        if nxt is not None and nxt.op in _CLOSING_ACTS:
+        # a GELU subgraph (erf or tanh form) closes the chain like a one-node activation: after the
+        # residual add, which is the order of the kernels' epilogue
+        gelu = match_gelu(g, c, cur.name)
+        if gelu is not None:
+            act, gnodes, out_node = gelu
+            chain += gnodes + [out_node]
+            cur = out_node
+        elif nxt is not None and nxt.op in _CLOSING_ACTS:
             act = _CLOSING_ACTS[nxt.op]
             chain.append(nxt)
             cur = nxt
@@ -1678,6 +1741,38 @@ def fuse_depthwise(g, order, fed, fetch_refs, device, opts):
             cur = nxt
         impl = FusedDepthwiseConv(w, bias, (strides[1], strides[2]), padding, pads, act, device, c.use_hip, cur.name)
         _finalize(g, chain, "_FusedDepthwiseConv2D", [x_ref], {"_impl": impl})
+        c.refresh()
+
+
+def fuse_depthwise_layernorm(g, order, fed, fetch_refs, device, opts):
+    """``_LayerNorm(_FusedDepthwiseConv2D(x))`` -> ``_FusedDepthwiseLN`` (the
+    opening of a ConvNeXt block) when the depthwise op is 7 x 7 / stride 1
+    without activation, the LayerNorm is its only reader, it is not fetched, and
+    gamma and beta have C elements or one each.  On the GPU also what
+    kernels/dwln.hip takes (C % 8 == 0, 8 <= C <= kDwLnMaxC).  Runs after
+    fuse_layernorm and fuse_depthwise; ``TFSERVE_DWLN=0`` keeps the pair."""
+    if os.environ.get("TFSERVE_DWLN", "1") == "0":
+        return
+    c = _Ctx(g, order, fed, fetch_refs, device, opts)
+    for name in order:
+        n = g.nodes.get(name)
+        if n is None or n.op != "_FusedDepthwiseConv2D":
+            continue
+        dw = n.attrs["_impl"]
+        if not FusedDepthwiseLN.shape_ok(dw):
+            continue
+        ln = c.only_consumer(name)
+        if ln is None or ln.op != "_LayerNorm" or ln.inputs != [(name, 0)]:
+            continue
+        limpl = ln.attrs["_impl"]
+        if any(v.numel() not in (1, dw.c) for v in (limpl.g, limpl.b)):
+            continue
+        if c.use_hip:
+            from ..ops import hip
+            if not hip().dwconv_ln_supported(1, 1, 1, dw.c, dw.kh, dw.kw, dw.sh, dw.sw):
+                continue
+        impl = FusedDepthwiseLN(dw, limpl, c.use_hip, ln.name)
+        _finalize(g, [n, ln], "_FusedDepthwiseLN", list(n.inputs), {"_impl": impl})
         c.refresh()
 
 
@@ -2328,6 +2423,7 @@ def default_passes(options=None):
     from .patterns import bert_passes, late_passes
     return [fuse_pools, fuse_softmax_argmax, fuse_hard_activations, fuse_swish, fuse_squeeze_excite,
             fuse_squeeze_excite_sigmoid] + bert_passes() + \
-        [fuse_grouped_conv, fuse_conv, fuse_depthwise, fuse_dual_conv, fuse_post_activation, fuse_stem_pool, fuse_matmul,
+        [fuse_grouped_conv, fuse_conv, fuse_depthwise, fuse_depthwise_layernorm,
+         fuse_dual_conv, fuse_post_activation, fuse_stem_pool, fuse_matmul,
          fuse_classifier_head, fuse_dense_softmax, fuse_conv_chain] + late_passes() + \
         [fuse_matmul_layernorm, defer_layernorm, release_weight_sources]

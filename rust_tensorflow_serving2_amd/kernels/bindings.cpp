@@ -5,6 +5,7 @@
 // pre-allocated outputs via the `out=` forms), and validates shapes on the host
 // before anything touches the GPU.
 #include <cstdlib>
+#include <cmath>
 #include <algorithm>
 #include <torch/extension.h>
 #include <ATen/hip/impl/HIPGuardImplMasqueradingAsCUDA.h>
@@ -534,6 +535,52 @@ Tensor dwconv2d(const Tensor& x, const Tensor& w, const Tensor& bias, int64_t KH
   check(tfsk::dwconv_nhwc_launch(bf16p(x), w.data_ptr<float>(), bias.data_ptr<float>(), bf16p_mut(y), int(N), int(H),
                                  int(W), int(C), int(KH), int(KW), int(SH), int(SW), int(PT), int(PL), int(Ho), int(Wo),
                                  int(act), int(strip), cur_stream(x)), "dwconv2d");
+  return y;
+}
+
+// Depthwise 7x7 conv + bias + LayerNorm over C in one launch (dwln.hip): x NHWC
+// bf16 (C % 8 == 0, 8 <= C <= kDwLnMaxC), w [49][C], bias, gamma, beta [C] f32
+// -> (LN_C(conv + bias) * gamma + beta) as [N][Ho][Wo][C] bf16, the conv result
+// in fp32 throughout.  Geometry as dwconv2d's; kh, kw, sh, sw are there to be
+// checked: the kernel is 7 x 7 / stride 1 only.
+Tensor dwconv_ln(const Tensor& x, const Tensor& w, const Tensor& bias, const Tensor& gamma, const Tensor& beta,
+                 double eps, int64_t PT, int64_t PL, int64_t Ho, int64_t Wo, const c10::optional<Tensor>& out,
+                 int64_t KH, int64_t KW, int64_t SH, int64_t SW) {
+  need(x, at::kBFloat16, "x");
+  need(w, at::kFloat, "w");
+  need(bias, at::kFloat, "bias");
+  need(gamma, at::kFloat, "gamma");
+  need(beta, at::kFloat, "beta");
+  TORCH_CHECK(KH == 7 && KW == 7, "dwconv_ln: the filter is 7 x 7 (got ", KH, " x ", KW, ")");
+  TORCH_CHECK(SH == 1 && SW == 1, "dwconv_ln: the stride is 1 (got ", SH, " x ", SW, ")");
+  TORCH_CHECK(x.dim() == 4, "dwconv_ln: x must be NHWC");
+  const int64_t N = x.size(0), H = x.size(1), W = x.size(2), C = x.size(3);
+  TORCH_CHECK(C % 8 == 0 && C >= 8 && C <= tfsk::kDwLnMaxC, "dwconv_ln: C % 8 == 0 and 8 <= C <= ", tfsk::kDwLnMaxC,
+              " (got ", C, " channels)");
+  TORCH_CHECK(PT >= 0 && PL >= 0 && Ho >= 1 && Wo >= 1, "dwconv_ln: bad geometry");
+  TORCH_CHECK(H >= 1 && W >= 1, "dwconv_ln: empty image");
+  // the last window must start inside the padded image: no output made of padding alone
+  TORCH_CHECK(Ho - 1 - PT < H && Wo - 1 - PL < W, "dwconv_ln: output larger than the input allows");
+  TORCH_CHECK(w.numel() == 49 * C, "dwconv_ln: w must be [49][C] (a 7 x 7 filter, channel multiplier 1), got ",
+              w.numel(), " elements for ", C, " channels");
+  TORCH_CHECK(bias.numel() == C, "dwconv_ln: bias must have C entries");
+  TORCH_CHECK(gamma.numel() == C && beta.numel() == C, "dwconv_ln: gamma and beta must have C entries (got ",
+              gamma.numel(), " and ", beta.numel(), " for ", C, " channels)");
+  TORCH_CHECK(eps >= 0.0 && std::isfinite(eps), "dwconv_ln: eps must be finite and >= 0");
+  TORCH_CHECK(w.device() == x.device() && bias.device() == x.device() && gamma.device() == x.device() &&
+              beta.device() == x.device(), "dwconv_ln: tensors on different devices");
+  TORCH_CHECK(x.numel() * 2 < 0x7ffffff0LL && N * Ho * Wo * C * 2 < 0x7ffffff0LL, "dwconv_ln operands must be < 2 GiB");
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
+  Tensor y = out.has_value() ? *out : torch::empty({N, Ho, Wo, C}, x.options());
+  need(y, at::kBFloat16, "out");
+  TORCH_CHECK(y.numel() == N * Ho * Wo * C && y.device() == x.device(), "out has the wrong size");
+  TORCH_CHECK(aligned16(x) && aligned16(w) && aligned16(bias) && aligned16(gamma) && aligned16(beta) && aligned16(y),
+              "dwconv_ln: tensors must be 16-B aligned");
+  if (y.numel() == 0) return y;
+  check(tfsk::dwconv_ln_launch(bf16p(x), w.data_ptr<float>(), bias.data_ptr<float>(), gamma.data_ptr<float>(),
+                               beta.data_ptr<float>(), bf16p_mut(y), int(N), int(H), int(W), int(C), int(KH), int(KW),
+                               int(SH), int(SW), int(PT), int(PL), int(Ho), int(Wo), float(eps), cur_stream(x)),
+        "dwconv_ln");
   return y;
 }
 
@@ -1084,6 +1131,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     const int k = tfsk::dwconv_forms(int(n), int(ho), int(wo), int(c), int(kh), int(kw), int(sh), int(sw), forms);
     return std::vector<int64_t>(forms, forms + k);
   }, "the strip values dwconv2d takes for the shape: [0], [0, 2, 8] (3 x 3 strips) or [0, 2, 4] (5 x 5 strips)");
+  m.def("dwconv_ln", &dwconv_ln, "depthwise 7x7 conv + bias + LayerNorm over C in one launch, NHWC bf16",
+        py::arg("x"), py::arg("w"), py::arg("bias"), py::arg("gamma"), py::arg("beta"), py::arg("eps"), py::arg("pt"),
+        py::arg("pl"), py::arg("ho"), py::arg("wo"), py::arg("out") = py::none(), py::arg("kh") = 7,
+        py::arg("kw") = 7, py::arg("sh") = 1, py::arg("sw") = 1);
+  m.def("dwconv_ln_supported", [](int64_t n, int64_t ho, int64_t wo, int64_t c, int64_t kh, int64_t kw, int64_t sh,
+                                  int64_t sw) {
+    return tfsk::dwconv_ln_supported(n, ho, wo, c, int(kh), int(kw), int(sh), int(sw));
+  }, "whether dwconv_ln takes the shape: 7 x 7, stride 1, C % 8 == 0, 8 <= C <= dwconv_ln_max_c");
+  m.def("dwconv_ln_grid", [](int64_t n, int64_t ho, int64_t wo, int64_t c) {
+    return int64_t(tfsk::dwconv_ln_grid(n, ho, wo, c));
+  }, "workgroups of the dwconv_ln launch for the shape (0: nothing to launch or unsupported)");
+  m.attr("dwconv_ln_max_c") = int64_t(tfsk::kDwLnMaxC);
   m.def("gconv2d", &gconv2d, "grouped 3x3 conv on MFMA: act(conv(x, w packed bf16) + bias), NHWC bf16", py::arg("x"),
         py::arg("w"), py::arg("bias"), py::arg("cg"), py::arg("sh"), py::arg("pt"), py::arg("pl"), py::arg("ho"),
         py::arg("wo"), py::arg("act") = 0, py::arg("out") = py::none(), py::arg("cg_out") = -1, py::arg("sw") = -1,

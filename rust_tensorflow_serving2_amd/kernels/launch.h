@@ -183,6 +183,23 @@ int dwconv_forms(int N, int Ho, int Wo, int C, int KH, int KW, int SH, int SW, i
 hipError_t dwconv_nhwc_launch(const uint16_t* x, const float* w, const float* bias, uint16_t* y, int N, int H, int W,
                               int C, int KH, int KW, int SH, int SW, int PT, int PL, int Ho, int Wo, int act,
                               int strip, hipStream_t stream);
+// Depthwise 7x7 / stride 1 conv + bias + LayerNorm over C in one launch
+// (dwln.hip): x [N][H][W][C] bf16, w [49][C], bias, gamma, beta [C] f32 ->
+// y [N][Ho][Wo][C] bf16 = LN_C(bias + conv)(eps) * gamma + beta, the conv
+// result kept in fp32 up to the one rounding of y.  C % 8 == 0, 8 <= C <=
+// kDwLnMaxC, explicit top / left padding, Ho / Wo from the caller (taps outside
+// the image read zero).  A workgroup owns kDwLnRowsTall or kDwLnRowsShort
+// output rows of a column tile (the launcher's choice); dwconv_ln_grid is its
+// workgroup count.  Anything else (dwconv_ln_supported is false, operands of
+// 2 GiB or more or not 16-B aligned) returns hipErrorInvalidValue and launches
+// nothing.
+constexpr int kDwLnMaxC = 1024;
+constexpr int kDwLnRowsTall = 4, kDwLnRowsShort = 2;
+bool dwconv_ln_supported(long N, long Ho, long Wo, long C, int KH, int KW, int SH, int SW);
+long dwconv_ln_grid(long N, long Ho, long Wo, long C);
+hipError_t dwconv_ln_launch(const uint16_t* x, const float* w, const float* bias, const float* gamma,
+                            const float* beta, uint16_t* y, int N, int H, int W, int C, int KH, int KW, int SH, int SW,
+                            int PT, int PL, int Ho, int Wo, float eps, hipStream_t stream);
 // NHWC bf16 grouped 3x3 conv on MFMA (gconv.hip): x [N][H][W][C], bias [C]
 // f32 -> y [N][Ho][Wo][C] bf16 = act(conv_grouped + bias), act in {kActNone,
 // kActRelu}.  CGin == CGout == Cg in {4, 8, 16, 32} channels per group, C % 8

@@ -1,11 +1,12 @@
 #!/usr/bin/env python
 """What does bf16 storage alone cost a MobileNet (or, with --family resnext, a
-ResNeXt-50 32x4d; with --family efficientnet, an EfficientNet-B0) end to end?
-CPU only.
+ResNeXt-50 32x4d; with --family efficientnet, an EfficientNet-B0; with --family
+convnext, a ConvNeXt-T) end to end?  CPU only.
 
 Exports a random-init model, runs the fp32 interpreter, and runs the fused
 CPU program a second time with the conv weights rounded to bf16 and the output of
-every fused conv / grouped conv / depthwise / squeeze-excite op rounded to bf16 -- what the GPU
+every fused conv / grouped conv / depthwise / depthwise + LayerNorm / LayerNorm / squeeze-excite op
+rounded to bf16 -- what the GPU
 program stores -- with everything else in fp32.  Prints, per input seed:
 
 * the fp32 interpreter's logit spread per row, its top-1 / top-2 margin, the
@@ -20,10 +21,12 @@ program stores -- with everything else in fp32.  Prints, per input seed:
 `--gated-gain` / `--expand-gain` override models/mobilenet.py's init gains
 (V3_GATED_PROJECT_GAIN / V3_EXPAND_GAIN) for the exported model, or, with
 --family efficientnet, models/efficientnet.py's GATED_PROJECT_GAIN / EXPAND_GAIN.
+`--layer-scale` overrides models/convnext.py's LAYER_SCALE_INIT.
 
     python scripts/bf16_emulation.py --version v3_small --seeds 0 1 2 3 --trials 3
     python scripts/bf16_emulation.py --family resnext --seeds 3 4 --trials 1
     python scripts/bf16_emulation.py --family efficientnet --seeds 0 1 2 --trials 3
+    python scripts/bf16_emulation.py --family convnext --seeds 0 1 2 --trials 3
 """
 import argparse
 import os
@@ -38,7 +41,8 @@ from rust_tensorflow_serving2_amd.models import mobilenet  # noqa: E402
 from rust_tensorflow_serving2_amd.server.servable import Servable, ServableOptions  # noqa: E402
 
 OUTS = ["classes", "probabilities"]
-ROUNDED = ("_FusedConv2D", "_FusedGroupedConv2D", "_FusedDepthwiseConv2D", "_SqueezeExcite", "_SqueezeExciteSigmoid")
+ROUNDED = ("_FusedConv2D", "_FusedGroupedConv2D", "_FusedDepthwiseConv2D", "_SqueezeExcite", "_SqueezeExciteSigmoid",
+           "_FusedDepthwiseLN", "_LayerNorm")
 
 
 def bf16(t):
@@ -75,10 +79,10 @@ def emulate(program, trial):
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
-    ap.add_argument("--family", default="mobilenet", choices=["mobilenet", "resnext", "efficientnet"],
+    ap.add_argument("--family", default="mobilenet", choices=["mobilenet", "resnext", "efficientnet", "convnext"],
                     help="resnext: ResNeXt-50 32x4d at full width (tests/test_resnext_gpu.py's model); efficientnet: "
-                         "EfficientNet-B0 at full width (tests/test_efficientnet_gpu.py's model); --version is "
-                         "MobileNet's")
+                         "EfficientNet-B0 at full width (tests/test_efficientnet_gpu.py's model); convnext: ConvNeXt-T "
+                         "at full width and depth (tests/test_convnext_gpu.py's model); --version is MobileNet's")
     ap.add_argument("--version", default="v3_small", choices=mobilenet.VERSIONS)
     ap.add_argument("--image-size", type=int, default=64)
     ap.add_argument("--model-seed", type=int, default=3)
@@ -87,6 +91,7 @@ def main():
     ap.add_argument("--trials", type=int, default=3)
     ap.add_argument("--gated-gain", type=float)
     ap.add_argument("--expand-gain", type=float)
+    ap.add_argument("--layer-scale", type=float)
     a = ap.parse_args()
     if a.gated_gain is not None:
         mobilenet.V3_GATED_PROJECT_GAIN = dict(mobilenet.V3_GATED_PROJECT_GAIN, **{a.version: a.gated_gain})
@@ -100,6 +105,12 @@ def main():
         if a.expand_gain is not None:
             efficientnet.EXPAND_GAIN = a.expand_gain
         print(a.version, "gated project gain", efficientnet.GATED_PROJECT_GAIN, "expand gain", efficientnet.EXPAND_GAIN)
+    elif a.family == "convnext":
+        from rust_tensorflow_serving2_amd.models import convnext
+        a.version = "convnext_tiny"
+        if a.layer_scale is not None:
+            convnext.LAYER_SCALE_INIT = a.layer_scale
+        print(a.version, "layer scale init", convnext.LAYER_SCALE_INIT)
     elif a.family == "resnext":
         a.version = "resnext50"
     elif a.version.startswith("v3"):
@@ -108,6 +119,8 @@ def main():
     path = os.path.join(tempfile.mkdtemp(), "1")
     if a.family == "efficientnet":
         efficientnet.export(path, image_size=a.image_size, seed=a.model_seed)
+    elif a.family == "convnext":
+        convnext.export(path, image_size=a.image_size, seed=a.model_seed, layer_scale_init=convnext.LAYER_SCALE_INIT)
     elif a.family == "resnext":
         from rust_tensorflow_serving2_amd.models import resnet
         resnet.export(path, groups=32, width_per_group=4, image_size=a.image_size, seed=a.model_seed)
