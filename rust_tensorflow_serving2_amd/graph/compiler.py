@@ -216,7 +216,7 @@ def _fold(g: Graph, order: List[str], fed: Set[str]) -> None:
 # Pure ops that are safe to merge when they have identical inputs and attrs.
 _CSE_OPS = {"Add", "AddV2", "Sub", "Mul", "RealDiv", "Maximum", "Minimum", "Neg", "ExpandDims", "Reshape",
             "Squeeze", "Cast", "Transpose", "StridedSlice", "Identity", "Exp", "Rsqrt", "Sqrt", "Tanh", "Relu",
-            "Pow", "SquaredDifference", "Mean", "Sum", "ConcatV2", "Pack", "Shape", "Fill", "Tile", "GatherV2",
+            "Pow", "SquaredDifference", "Mean", "Sum", "ConcatV2", "Pack", "Shape", "Fill", "Tile", "BroadcastTo", "GatherV2",
             "OneHot", "BiasAdd", "Softmax", "Erf"}
 
 

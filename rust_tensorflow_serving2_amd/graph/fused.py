@@ -38,6 +38,9 @@ a single consumer and is not fetched):
 * ``Mean(NHWC, axes=[1,2])`` => ``_GlobalAvgPool``;  ``MaxPool`` => ``_MaxPool``;
   the ResNet stem ``_FusedConv2D(7x7/2, RGB) -> _MaxPool(3x3/2)`` => ``_StemPool``.
 * ``Softmax(x)`` + ``ArgMax(x, -1)`` on the same logits => ``_SoftmaxArgMax``.
+* ViT: ``AddV2(ConcatV2([Tile|BroadcastTo(cls, [batch, ..]), Reshape(x, [-1, P, C])], 1), pos)``
+  => ``_PatchTokens(x, batch)``: class token, patches and position embedding in one
+  ``patch_tokens`` launch (kernels/misc.hip) from an fp32 ``[P + 1, C]`` table.
 * BERT: decomposed LayerNorm => ``_LayerNorm``; tanh/erf GELU subgraphs => act
   of the producing ``_FusedMatMul``; Q/K/V projections + attention core =>
   ``_FusedQKV`` + ``_Attention`` (see ``bert_passes``).
@@ -1060,7 +1063,7 @@ def _impl_op(ctx, node, ins):
 for _op in ("_FusedConv2D", "_FusedDepthwiseConv2D", "_FusedDepthwiseLN", "_FusedGroupedConv2D", "_FusedDualConv", "_FusedMatMul", "_GlobalAvgPool", "_MaxPool",
             "_SqueezeExcite", "_SqueezeExciteSigmoid",
             "_SoftmaxArgMax", "_LayerNorm",
-            "_FusedQKV", "_Attention", "_EmbeddingLN", "_KeyMaskAdder", "_DenseSoftmax"):
+            "_FusedQKV", "_Attention", "_EmbeddingLN", "_KeyMaskAdder", "_DenseSoftmax", "_PatchTokens"):
     O.OPS[_op] = _impl_op
 
 
@@ -1776,6 +1779,135 @@ def fuse_depthwise_layernorm(g, order, fed, fetch_refs, device, opts):
         c.refresh()
 
 
+# ------------------------------------------------------------------ ViT patch tokens
+class PatchTokens:
+    """``AddV2(ConcatV2([cls_b, Reshape(x, [-1, P, C])], axis=1), pos)`` with
+    ``cls_b`` the ``[1, 1, C]`` class token repeated ``batch`` times (the op's
+    second input: the graph's own ``Shape -> StridedSlice`` scalar).  The pass
+    sees constants only; whether ``x`` is the patch conv's ``[B, H, W, C]``
+    output with ``H * W == P`` is known at the call.  Then, on the GPU, one
+    ``patch_tokens`` launch from the fp32 table (row 0 = class token + pos[0],
+    rows 1.. = pos[1..]); any other input, and the CPU, gets the replaced
+    nodes' own semantics from torch."""
+
+    def __init__(self, cls: torch.Tensor, pos: torch.Tensor, p: int, c: int, device, use_hip: bool, name: str):
+        self.p, self.c = int(p), int(c)
+        self.use_hip = use_hip
+        self.name = name
+        self.cls = to_device(cls.float().reshape(1, 1, self.c), device)
+        self.pos = to_device(pos.float().reshape(self.p + 1, self.c), device)
+        self.pos_rank = pos.dim()
+        table = pos.float().reshape(self.p + 1, self.c).clone()
+        if not table.is_meta:
+            table[0] += cls.float().reshape(self.c)
+        self.table = to_device(table, device) if use_hip else None
+
+    def __call__(self, ctx, node, ins):
+        x = O.to_torch(ins[0])
+        batch = O.host_int(ins[1])
+        P, C = self.p, self.c
+        if (self.use_hip and x.is_cuda and x.dim() == 4 and x.shape[1] * x.shape[2] == P and x.shape[3] == C
+                and x.shape[0] == batch):
+            from ..ops import hip
+            H = hip()
+            if H.patch_tokens_supported(batch, P, C):
+                return [H.patch_tokens(_to_bf16(x).contiguous().view(batch, P, C), self.table)]
+        try:
+            r = x.reshape(-1, P, C)
+        except RuntimeError as e:
+            raise O.OpError(f"{node.name}: cannot reshape {list(x.shape)} to [-1, {P}, {C}]: {e}") from None
+        cls, pos = self.cls.to(x.device), self.pos.to(x.device)
+        y = torch.cat([cls.repeat(batch, 1, 1), r.float()], dim=1) + (pos if self.pos_rank == 2 else pos.unsqueeze(0))
+        return [y.to(x.dtype) if x.is_cuda and x.dtype == BF16 else y]
+
+
+def _batch_scalar(g: Graph, ref) -> bool:
+    """``ref`` = StridedSlice(Shape(.), ..): a run-time scalar of the graph's own."""
+    ss = g.nodes.get(ref[0])
+    if ss is None or ref[1] != 0 or ss.op != "StridedSlice" or not ss.inputs:
+        return False
+    sh = g.nodes.get(ss.inputs[0][0])
+    return sh is not None and sh.op == "Shape"
+
+
+def _repeated_token(g: Graph, ref, c_hint=None):
+    """``ref`` = Tile(cls[1, 1, C], Pack([batch, 1, 1])) or BroadcastTo(cls[1, 1, C],
+    Pack([batch, 1, C])) -> (cls, batch ref, [rep, pack]) or None."""
+    rep = g.nodes.get(ref[0])
+    if rep is None or ref[1] != 0 or rep.op not in ("Tile", "BroadcastTo") or len(rep.inputs) != 2:
+        return None
+    cls = _const(g, rep.inputs[0])
+    pack = g.nodes.get(rep.inputs[1][0])
+    if cls is None or cls.dim() != 3 or cls.shape[0] != 1 or cls.shape[1] != 1 or not cls.is_floating_point():
+        return None
+    if pack is None or rep.inputs[1][1] != 0 or pack.op != "Pack" or len(pack.inputs) != 3 or \
+            int(pack.attr("axis", 0)) != 0:
+        return None
+    if not _batch_scalar(g, pack.inputs[0]):
+        return None
+    want = (1, 1) if rep.op == "Tile" else (1, int(cls.shape[2]))
+    for r, w in zip(pack.inputs[1:], want):
+        v = _const(g, r)
+        if v is None or v.numel() != 1 or v.dim() != 0 or int(v) != w:
+            return None
+    return cls, pack.inputs[0], [rep, pack]
+
+
+def fuse_patch_tokens(g, order, fed, fetch_refs, device, opts):
+    """The front of a ViT behind its patch conv ->  ``_PatchTokens(x, batch)``
+    (class PatchTokens has the pattern).  Matched by shape: the class token is
+    ``[1, 1, C]``, the reshape's target ``[-1, P, C]``, the concat on axis 1
+    with the token first, ``pos`` a ``[1, P + 1, C]`` or ``[P + 1, C]``
+    constant on either side of the add.  The concat, the reshape, the repeat
+    and its Pack must be read inside the pattern only and not be fetched.
+    Runs after fuse_conv, so ``x`` is the fused conv's output."""
+    c = _Ctx(g, order, fed, fetch_refs, device, opts)
+    for name in order:
+        add = g.nodes.get(name)
+        if add is None or add.op not in ("Add", "AddV2") or len(add.inputs) != 2:
+            continue
+        for cat_ref, pos_ref in ((add.inputs[0], add.inputs[1]), (add.inputs[1], add.inputs[0])):
+            cat = g.nodes.get(cat_ref[0])
+            pos = _const(g, pos_ref)
+            if cat is None or cat_ref[1] != 0 or cat.op != "ConcatV2" or len(cat.inputs) != 3 or pos is None:
+                continue
+            axis = _const(g, cat.inputs[2])
+            if axis is None or axis.numel() != 1 or int(axis.reshape(-1)[0]) != 1:
+                continue
+            tok = _repeated_token(g, cat.inputs[0])
+            rs = g.nodes.get(cat.inputs[1][0])
+            if tok is None or rs is None or cat.inputs[1][1] != 0 or rs.op != "Reshape":
+                continue
+            cls, batch_ref, rep_nodes = tok
+            shp = _const(g, rs.inputs[1])
+            if shp is None or shp.numel() != 3:
+                continue
+            lead, P, C = [int(v) for v in shp.reshape(-1).tolist()]
+            if lead != -1 or P < 1 or C != int(cls.shape[2]) or not pos.is_floating_point():
+                continue
+            if tuple(pos.shape) not in ((1, P + 1, C), (P + 1, C)):
+                continue
+            interior = [cat, rs] + rep_nodes
+            names = {n.name for n in interior} | {add.name}
+            if any(n.name in c.fetch_nodes or any(cn not in names for cn, _p, _i in c.cons.get(n.name, []))
+                   for n in interior):
+                continue
+            # each inner value read once: the concat by the add, the reshape and the repeat by the concat
+            if any(len(c.cons.get(n.name, [])) != 1 for n in interior):
+                continue
+            impl = PatchTokens(cls, pos, P, C, device, c.use_hip, add.name)
+            ctrl = _merge_ctrl(interior + [add])
+            for n in interior:
+                del g.nodes[n.name]
+            add.op = "_PatchTokens"
+            add.inputs = [rs.inputs[0], batch_ref]
+            add.ctrl = ctrl
+            add.attrs = {"_impl": impl}
+            add.value = None
+            c.refresh()
+            break
+
+
 # ------------------------------------------------------------------ hard activations (MobileNetV3)
 def _hard_sigmoid_op(ctx, node, ins):
     """clamp(x + 3, 0, 6) * c with the graph's own c (1/6 within 1e-4), in the
@@ -2423,7 +2555,7 @@ def default_passes(options=None):
     from .patterns import bert_passes, late_passes
     return [fuse_pools, fuse_softmax_argmax, fuse_hard_activations, fuse_swish, fuse_squeeze_excite,
             fuse_squeeze_excite_sigmoid] + bert_passes() + \
-        [fuse_grouped_conv, fuse_conv, fuse_depthwise, fuse_depthwise_layernorm,
+        [fuse_grouped_conv, fuse_conv, fuse_patch_tokens, fuse_depthwise, fuse_depthwise_layernorm,
          fuse_dual_conv, fuse_post_activation, fuse_stem_pool, fuse_matmul,
          fuse_classifier_head, fuse_dense_softmax, fuse_conv_chain] + late_passes() + \
         [fuse_matmul_layernorm, defer_layernorm, release_weight_sources]

@@ -391,6 +391,22 @@ def _tile(ctx, n, ins):
     return [to_torch(ins[0]).repeat(host_ints(ins[1]))]
 
 
+@op("BroadcastTo")
+def _broadcast_to(ctx, n, ins):
+    """tf.broadcast_to: numpy broadcasting of the input against ``shape``, which
+    may have more axes than the input (they are added in front)."""
+    if isinstance(ins[0], np.ndarray) and ins[0].dtype == object:
+        raise Unsupported("BroadcastTo on strings")
+    x = to_torch(ins[0])
+    shape = host_ints(ins[1])
+    if len(shape) < x.dim() or any(d < 0 for d in shape):
+        raise OpError(f"{n.name}: cannot broadcast {list(x.shape)} to {shape}")
+    try:
+        return [x.expand(shape).contiguous()]
+    except RuntimeError as e:
+        raise OpError(f"{n.name}: cannot broadcast {list(x.shape)} to {shape}: {e}") from None
+
+
 @op("Slice")
 def _slice(ctx, n, ins):
     x = to_torch(ins[0])

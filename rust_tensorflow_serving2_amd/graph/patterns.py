@@ -144,6 +144,7 @@ MAX_ATTENTION_SEQ = 4096      # kernels/launch.h kMaxAttentionSeq
 class AttentionOp:
     def __init__(self, heads: int, head_dim: int, seq: int, scale: float, use_hip: bool):
         self.h, self.d, self.s, self.scale, self.use_hip = heads, head_dim, seq, scale, use_hip
+        self.form = None              # None: ops.tuned_choice picks among attention_forms(S); 0 / 1 forced
 
     def __call__(self, ctx, node, ins):
         qkv = O.to_torch(ins[0])
@@ -163,8 +164,23 @@ class AttentionOp:
                 mask = adder.float().contiguous().to(qkv.device)
                 bstride = S * adder.shape[2] if adder.shape[0] == B and B > 1 else 0
                 qstride = S if adder.shape[2] == S else 0
-            y = hip().attention(q3, mask, H, self.scale, None, bstride, qstride)
-            return [y.reshape(B * S, H * D)]
+            kernels = hip()
+            forms = [int(f) for f in kernels.attention_forms(S)]
+            if len(forms) == 1:
+                y = kernels.attention(q3, mask, H, self.scale, None, bstride, qstride)
+                return [y.reshape(B * S, H * D)]
+            # a length with two kernels (kernels/attention.hip: the KV-block loop, form 0, or the
+            # register kernel padded to 32 keys, form 1): timed per shape under a key of its own
+            out = torch.empty((B, S, H * D), device=q3.device, dtype=BF16)
+
+            def run(form):
+                return kernels.attention(q3, mask, H, self.scale, out, bstride, qstride, form)
+            layout = "none" if mask is None else ("query" if qstride else "key")
+            pick = self.form
+            if pick is None:
+                from ..ops import tuned_choice
+                pick = tuned_choice(("attn", B, S, H, layout), {f: (lambda f=f: run(f)) for f in forms}, default=0)
+            return [run(pick).reshape(B * S, H * D)]
         q, k, v = qkv.float().reshape(B, S, 3, H, D).permute(2, 0, 3, 1, 4)
         sc = q @ k.transpose(-1, -2) * self.scale
         if adder is not None:
@@ -419,7 +435,7 @@ def fuse_attention(g, order, fed, fetch_refs, device, opts):
         if cur is not None and cur.op in ("Add", "AddV2"):
             # scores + adder (either order): scores side is the Mul/BatchMatMul
             a0, a1 = _node(g, cur.inputs[0]), _node(g, cur.inputs[1])
-            if a0 is not None and a0.op in ("Mul", "BatchMatMul", "BatchMatMulV2", "BatchMatMulV3"):
+            if a0 is not None and a0.op in ("Mul", "RealDiv", "BatchMatMul", "BatchMatMulV2", "BatchMatMulV3"):
                 adder_ref, cur2 = cur.inputs[1], a0
             else:
                 adder_ref, cur2 = cur.inputs[0], a1
@@ -436,6 +452,15 @@ def fuse_attention(g, order, fed, fetch_refs, device, opts):
             scale = sv
             interior.append(cur)
             cur = nxt
+        elif cur is not None and cur.op == "RealDiv" and len(cur.inputs) == 2:
+            # the TF ViT spelling: scores / sqrt(d).  Only a scalar divisor (by shape: a [S] constant
+            # of equal entries is not one), never zero, and only on the right
+            dv = _const_t(g, cur.inputs[1])
+            if dv is None or dv.numel() != 1 or dv.dim() != 0 or not dv.is_floating_point() or float(dv) == 0.0:
+                continue
+            scale = 1.0 / float(dv)
+            interior.append(cur)
+            cur = _node(g, cur.inputs[0])
         qk = cur
         if qk is None or qk.op not in ("BatchMatMul", "BatchMatMulV2", "BatchMatMulV3") or \
                 qk.attr("adj_x", False) or not qk.attr("adj_y", False):

@@ -16,7 +16,9 @@
 // (attention_plds_kernel: the previous layout, P through a per-wave LDS strip.)
 // S in {64, 128, 192, 256} (the whole key row in registers; D == 64), and
 // attention_flash_kernel below for any other S up to
-// kMaxAttentionSeq.  The S x S matrix never touches HBM.
+// kMaxAttentionSeq.  attention_ragged_kernel (form 1) is the register kernel
+// for any 1 <= S <= 256, padded to 32 keys by the buffer descriptors (ViT's
+// 197, 50, 65).  The S x S matrix never touches HBM.
 #include <cstdlib>
 
 #include "common.h"
@@ -272,6 +274,250 @@ __global__ __launch_bounds__(QB * 4) void attention_kernel(const uint16_t* __res
     const int c = j * 64 + lane, row = c >> 3, ch = c & 7;
     *reinterpret_cast<uint4*>(ctx + (long(b) * S + q0 + row) * (long(H) * D) + h * D + ch * 8) =
         *reinterpret_cast<const uint4*>(os + row * D + ((ch ^ (row & 7)) * 8));
+  }
+  if (trace != nullptr) {
+    __builtin_amdgcn_s_waitcnt(0);          // this wave's stores acknowledged
+    attn_stamp(trace, trace_cap, 4);
+  }
+}
+
+// ---------------------------------------------------------------- any S <= 256
+// The same kernel for a run-time 1 <= S <= SP, SP = max(64, ceil32(S)) the
+// compile-time padded length (ViT: 197 -> 224, 50 -> 64, 65 -> 96).  What the
+// padding changes:
+//  * rows >= S come from the descriptors, never from memory: the qkv resource
+//    spans image b's S rows, a K row / V row / Q row past S gets kOOB as its
+//    whole offset and reads zeros (no access straddles the record count: every
+//    16-B chunk lies inside one row);
+//  * the key mask lands by 4-B LDS-DMA, one dword per lane (S * 4 bytes need
+//    not be a multiple of 16 and image b's mask row need not be 16-B aligned: a
+//    dword is wholly in range or wholly out);
+//  * every element of Ks [SP][64], Vt [64][0, SP) and Ms [0, SP) is written by
+//    this launch -- threads tid < SP stage V block tid (zeros past S), so the
+//    closed keys' exact-zero P meets zeros, not stale LDS; only the threads
+//    tid >= SP park their (zero) blocks in the rows' padding;
+//  * keys >= S are closed by a select to -inf after score * scale + mask and
+//    before the row maximum (only the last two key tiles can hold one when
+//    SP > 64: S > SP - 32);
+//  * query rows >= S are computed (Q = 0) and dropped: the output leaves by
+//    buffer stores through a resource bounded to image b's S rows, two per
+//    thread whatever S is; a wave whose 16 rows are all dead still stages and
+//    meets both barriers.
+template <int SP, int QB>
+__global__ __launch_bounds__(QB * 4) void attention_ragged_kernel(const uint16_t* __restrict__ qkv,
+                                                                  const float* __restrict__ mask_bias,
+                                                                  uint16_t* __restrict__ ctx, int S, int H,
+                                                                  float scale, long mask_bstride, long mask_qstride,
+                                                                  long long* __restrict__ trace, int trace_cap) {
+  attn_stamp(trace, trace_cap, 0);
+  constexpr int NTH = QB * 4;            // QB / 16 waves
+  constexpr int VT_LD = SP + 8;          // Vt row stride (elements): +16 B pad
+  constexpr int NT = SP / 16;            // key tiles
+  constexpr int NT_LIVE = SP == 64 ? 0 : NT - 2;   // tiles below hold live keys only
+  static_assert(SP % 32 == 0 && SP >= 64 && SP <= 256, "padded length");
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  uint16_t* Ks = reinterpret_cast<uint16_t*>(smem);          // [SP][64] swizzled
+  uint16_t* Vt = Ks + SP * D;                                 // [64][VT_LD]
+  float* Ms = reinterpret_cast<float*>(Vt + D * VT_LD);       // [256] key mask adder
+
+  const int qblocks = (S + QB - 1) / QB;
+  const int bid = blockIdx.x;
+  const int qb = bid % qblocks;
+  const int h = (bid / qblocks) % H;
+  const int b = bid / (qblocks * H);
+  const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int fr = lane & 15, fq = lane >> 4;
+  const long row_stride = 3L * H * D;
+  const uint16_t* base = qkv + long(b) * S * row_stride;
+
+  typedef __attribute__((address_space(3))) void* lds_ptr_t;
+  constexpr int NW = NTH / 64;
+  const __amdgpu_buffer_rsrc_t rsQ =
+      __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(base), 0, int(S * row_stride * 2), 0x00020000);
+  static_assert((SP / 8) % NW == 0, "K staging split");
+  constexpr int KDMA = SP / 8 / NW;
+#pragma unroll
+  for (int i = 0; i < KDMA; ++i) {
+    const int pc = wid + i * NW, key = pc * 8 + (lane >> 3);
+    const uint32_t src = uint32_t(long(key) * row_stride + H * D + h * D + (((lane & 7) ^ (key & 7)) * 8)) * 2u;
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsQ, (lds_ptr_t)(Ks + pc * 512), 16, key < S ? src : gemm::kOOB, 0, 0,
+                                             0);
+  }
+  // the [B,1,1,S] key mask, 64 keys per wave (a 0-record descriptor, zeros,
+  // when the mask is per query row or absent; zeros past S)
+  const bool key_mask = mask_bias != nullptr && mask_qstride == 0;
+  const __amdgpu_buffer_rsrc_t rsM = __builtin_amdgcn_make_buffer_rsrc(
+      const_cast<float*>(key_mask ? mask_bias + long(b) * mask_bstride : mask_bias), 0, key_mask ? S * 4 : 0,
+      0x00020000);
+  static_assert(SP <= 64 * NW, "mask staging");
+  if (wid * 64 < SP) {
+    const int key = wid * 64 + lane;
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsM, (lds_ptr_t)(Ms + wid * 64), 4,
+                                             key < S ? uint32_t(key) * 4u : gemm::kOOB, 0, 0, 0);
+  }
+  asm volatile("" ::: "memory");
+  __builtin_amdgcn_sched_barrier(0);
+  // ---- Q fragments (zeros for the query rows past S)
+  const int q0 = qb * QB + wid * 16;
+  bf16x8 qf[2];
+#pragma unroll
+  for (int kk = 0; kk < 2; ++kk)
+    qf[kk] = __builtin_bit_cast(
+        bf16x8, __builtin_amdgcn_raw_buffer_load_b128(
+                    rsQ, q0 + fr < S ? uint32_t(long(q0 + fr) * row_stride + h * D + kk * 32 + fq * 8) * 2u : gemm::kOOB,
+                    0, 0));
+  static_assert(SP <= NTH, "V staging split");
+  // V: the 8-key x 8-dim block tid of the SP / 8 x 8 blocks (keys past S read
+  // zeros; threads >= SP hold zeros and store them into the rows' padding)
+  const int kg = tid >> 3, vch = tid & 7;
+  uint32_t w[8][4];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    const int key = kg * 8 + k;
+    const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(
+        rsQ, key < S ? uint32_t(long(key) * row_stride + 2 * H * D + h * D + vch * 8) * 2u : gemm::kOOB, 0, 0);
+    w[k][0] = v.x; w[k][1] = v.y; w[k][2] = v.z; w[k][3] = v.w;
+  }
+  asm volatile("" ::: "memory");
+  __builtin_amdgcn_sched_barrier(0);
+  // K, the mask and Q landed (in order: only the 8 V loads may be younger)
+  gemm::wait_vmcnt<8>();
+  __syncthreads();
+  attn_stamp(trace, trace_cap, 1);          // Q / K / mask staged (V in flight)
+
+  // ---- S^T tiles: lane holds keys nt*16 + 4fq + r of query fr
+  f32x4 s[NT];
+#pragma unroll
+  for (int nt = 0; nt < NT; ++nt) {
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    const int key = nt * 16 + fr;
+#pragma unroll
+    for (int kk = 0; kk < 2; ++kk) {
+      const int ch = kk * 4 + fq;
+      const bf16x8 kf = *reinterpret_cast<const bf16x8*>(Ks + key * D + ((ch ^ (key & 7)) * 8));
+      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf[kk], acc, 0, 0, 0);
+    }
+    s[nt] = acc;
+  }
+  // ---- softmax over the live keys: key nt*16 + 4fq + r is live iff nt*16 + r < lim
+  const int lim = S - fq * 4;
+  float mx = -INFINITY;
+  if (key_mask) {
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) {
+      const f32x4 mb = *reinterpret_cast<const f32x4*>(Ms + nt * 16 + fq * 4);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        float v = s[nt][r] * scale + mb[r];
+        if (nt >= NT_LIVE) v = nt * 16 + r < lim ? v : -INFINITY;
+        s[nt][r] = v;
+        mx = fmaxf(mx, v);
+      }
+    }
+  } else {
+    // per-query adder: plain loads, clamped to a live row and a live key
+    const float* mq =
+        mask_bias ? mask_bias + long(b) * mask_bstride + long(min(q0 + fr, S - 1)) * mask_qstride : nullptr;
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int key = nt * 16 + fq * 4 + r;
+        float v = s[nt][r] * scale + (mq ? mq[nt >= NT_LIVE ? min(key, S - 1) : key] : 0.f);
+        if (nt >= NT_LIVE) v = nt * 16 + r < lim ? v : -INFINITY;
+        s[nt][r] = v;
+        mx = fmaxf(mx, v);
+      }
+    }
+  }
+  mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+  mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+  float sum = 0.f;
+  bf16x8 pb[SP / 32];                       // P^T B fragments, k-slot j -> tile 2ks + (j >> 2), r = j & 3
+  constexpr float kLog2e = 1.4426950408889634f;
+  const float mxl = mx * kLog2e;
+  typedef __attribute__((ext_vector_type(2))) float f32x2;
+  f32x2 sum2 = {0.f, 0.f};
+#pragma unroll
+  for (int ks = 0; ks < SP / 32; ++ks) {
+#pragma unroll
+    for (int j = 0; j < 8; j += 2) {
+      const f32x2 v = {s[2 * ks + (j >> 2)][j & 3], s[2 * ks + (j >> 2)][(j & 3) + 1]};
+      const f32x2 a = v * kLog2e - mxl;     // -inf for a closed key: p = 0 exactly
+      const f32x2 e = {__builtin_amdgcn_exp2f(a.x), __builtin_amdgcn_exp2f(a.y)};
+      sum2 += e;
+      pb[ks][j] = static_cast<__bf16>(e.x);
+      pb[ks][j + 1] = static_cast<__bf16>(e.y);
+    }
+  }
+  sum = sum2.x + sum2.y;
+  sum += __shfl_xor(sum, 16, 64);
+  sum += __shfl_xor(sum, 32, 64);
+  attn_stamp(trace, trace_cap, 2);          // scores + softmax done
+
+  // ---- V transposed into LDS (8 x 16-B stores per thread) behind the second barrier
+#pragma unroll
+  for (int d = 0; d < 8; ++d) {
+    uint32_t o[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const uint32_t lo = (d & 1) ? (w[2 * j][d >> 1] >> 16) : (w[2 * j][d >> 1] & 0xffffu);
+      const uint32_t hi = (d & 1) ? (w[2 * j + 1][d >> 1] & 0xffff0000u) : (w[2 * j + 1][d >> 1] << 16);
+      o[j] = lo | hi;
+    }
+    const int vcol = tid < SP ? kg * 8 : SP;
+    *reinterpret_cast<uint4*>(Vt + (vch * 8 + d) * VT_LD + vcol) = make_uint4(o[0], o[1], o[2], o[3]);
+  }
+  __syncthreads();
+
+  // ---- ctx^T = V^T P^T: A = Vt rows dt*16 + fr at the same permuted keys
+  f32x4 o[4];
+#pragma unroll
+  for (int dt = 0; dt < 4; ++dt) o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+  constexpr int KS = SP / 32;
+  bf16x8 va[KS][4];
+  auto read_v = [&](int ks) {
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt) {
+      const uint16_t* vr = Vt + (dt * 16 + fr) * VT_LD + ks * 32 + fq * 4;
+      const uint2 lo = *reinterpret_cast<const uint2*>(vr);
+      const uint2 hi = *reinterpret_cast<const uint2*>(vr + 16);
+      va[ks][dt] = __builtin_bit_cast(bf16x8, make_uint4(lo.x, lo.y, hi.x, hi.y));
+    }
+  };
+  read_v(0);
+  if (KS > 1) read_v(1);
+#pragma unroll
+  for (int ks = 0; ks < KS; ++ks) {
+    if (ks + 2 < KS) read_v(ks + 2);
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt) o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(va[ks][dt], pb[ks], o[dt], 0, 0, 0);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  attn_stamp(trace, trace_cap, 3);          // P V done (wave 0)
+  // ---- normalise, re-lay out through this wave's 16 x 64 block of the K rows
+  // ((wid + 1) * 16 <= 64 <= SP) and store whole 128-B rows; dead rows get kOOB
+  const float inv = 1.f / sum;
+  uint16_t* os = Ks + wid * 16 * D;
+#pragma unroll
+  for (int dt = 0; dt < 4; ++dt) {
+    const uint32_t lo = gemm::pack_bf16x2(o[dt][0] * inv, o[dt][1] * inv);
+    const uint32_t hi = gemm::pack_bf16x2(o[dt][2] * inv, o[dt][3] * inv);
+    const int chunk = dt * 2 + (fq >> 1);
+    *reinterpret_cast<uint2*>(os + fr * D + ((chunk ^ (fr & 7)) * 8) + (fq & 1) * 4) = make_uint2(lo, hi);
+  }
+  __builtin_amdgcn_s_waitcnt(0xc07f);          // lgkmcnt(0): this wave's LDS writes landed
+  __builtin_amdgcn_wave_barrier();
+  const long out_stride = long(H) * D;
+  const __amdgpu_buffer_rsrc_t rsO =
+      __builtin_amdgcn_make_buffer_rsrc(ctx + long(b) * S * out_stride, 0, int(S * out_stride * 2), 0x00020000);
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const int c = j * 64 + lane, row = c >> 3, ch = c & 7;
+    const u32x4 v = *reinterpret_cast<const u32x4*>(os + row * D + ((ch ^ (row & 7)) * 8));
+    __builtin_amdgcn_raw_buffer_store_b128(
+        v, rsO, q0 + row < S ? uint32_t(long(q0 + row) * out_stride + h * D + ch * 8) * 2u : gemm::kOOB, 0, 0);
   }
   if (trace != nullptr) {
     __builtin_amdgcn_s_waitcnt(0);          // this wave's stores acknowledged
@@ -698,6 +944,24 @@ int attn_qb(int BH) {
   return v ? v : (BH >= 256 ? 128 : 64);
 }
 
+// the ragged kernel at the padded length SP = max(64, ceil32(S)); QB = 64
+template <int SP>
+hipError_t launch_ragged(const uint16_t* qkv, const float* mb, uint16_t* ctx, int B, int S, int H, float scale, long bs,
+                         long qs, hipStream_t st) {
+  constexpr int QB = 64;
+  const long grid = long(B) * H * ((S + QB - 1) / QB);
+  // the descriptors count bytes in 32 bits: one image's qkv rows must fit
+  if (grid >= (1L << 31) || long(S) * 3 * H * D * 2 >= (1L << 31)) return hipErrorInvalidValue;
+  if (grid == 0) return hipSuccess;
+  constexpr int lds = (SP * D + D * (SP + 8)) * 2 + 1024;        // + the key mask's 1-KB DMA image
+  static_assert(lds <= 160 * 1024, "attention tile");
+  hipError_t e = ensure_dyn_lds(reinterpret_cast<const void*>(&attention_ragged_kernel<SP, QB>), lds);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL((attention_ragged_kernel<SP, QB>), dim3(unsigned(grid)), dim3(QB * 4), lds, st, qkv, mb, ctx, S,
+                     H, scale, bs, qs, g_attn_trace, g_attn_trace_cap);
+  return hipGetLastError();
+}
+
 }  // namespace
 
 int attention_set_plds(int mode) {
@@ -712,9 +976,22 @@ void attention_set_trace(long long* trace, int cap) {
 }
 
 hipError_t attention_launch(const uint16_t* qkv, const float* mask_bias, uint16_t* ctx, int B, int S, int H,
-                            int Dh, float scale, long mask_bstride, long mask_qstride, hipStream_t st) {
+                            int Dh, float scale, long mask_bstride, long mask_qstride, int form, hipStream_t st) {
   if (Dh != D) return hipErrorInvalidValue;
   const long bs = mask_bstride, qs = mask_qstride;
+  if (form == kAttnFormRagged) {
+    if (S < 1 || S > kAttnRaggedMaxSeq) return hipErrorInvalidValue;
+    switch (attention_ragged_sp(S)) {
+      case 64: return launch_ragged<64>(qkv, mask_bias, ctx, B, S, H, scale, bs, qs, st);
+      case 96: return launch_ragged<96>(qkv, mask_bias, ctx, B, S, H, scale, bs, qs, st);
+      case 128: return launch_ragged<128>(qkv, mask_bias, ctx, B, S, H, scale, bs, qs, st);
+      case 160: return launch_ragged<160>(qkv, mask_bias, ctx, B, S, H, scale, bs, qs, st);
+      case 192: return launch_ragged<192>(qkv, mask_bias, ctx, B, S, H, scale, bs, qs, st);
+      case 224: return launch_ragged<224>(qkv, mask_bias, ctx, B, S, H, scale, bs, qs, st);
+      default: return launch_ragged<256>(qkv, mask_bias, ctx, B, S, H, scale, bs, qs, st);
+    }
+  }
+  if (form != 0) return hipErrorInvalidValue;
   switch (S) {
     case 64: return launch_s<64>(qkv, mask_bias, ctx, B, H, scale, bs, qs, st);
     case 128:

@@ -1053,7 +1053,7 @@ Tensor embed_ln(const Tensor& ids, const c10::optional<Tensor>& type_ids, const 
 }
 
 Tensor attention(const Tensor& qkv, const c10::optional<Tensor>& mask_bias, int64_t heads, double scale,
-                 const c10::optional<Tensor>& out, int64_t mask_bstride, int64_t mask_qstride) {
+                 const c10::optional<Tensor>& out, int64_t mask_bstride, int64_t mask_qstride, int64_t form) {
   need(qkv, at::kBFloat16, "qkv");
   TORCH_CHECK(qkv.dim() == 3, "qkv must be [B, S, 3*H*D]");
   c10::hip::HIPGuardMasqueradingAsCUDA guard(qkv.device());
@@ -1061,7 +1061,14 @@ Tensor attention(const Tensor& qkv, const c10::optional<Tensor>& mask_bias, int6
   TORCH_CHECK(HD3 % (3 * heads) == 0, "qkv width must be 3*heads*head_dim");
   const int D = HD3 / (3 * heads);
   TORCH_CHECK(D == 64, "attention kernel supports head_dim 64");
+  TORCH_CHECK(form == 0 || form == tfsk::kAttnFormRagged, "attention: unknown form ", form, " (0 or 1)");
   TORCH_CHECK(S >= 1 && S <= tfsk::kMaxAttentionSeq, "attention kernel supports 1 <= S <= ", tfsk::kMaxAttentionSeq);
+  if (form == tfsk::kAttnFormRagged) {
+    TORCH_CHECK(S <= tfsk::kAttnRaggedMaxSeq, "attention form 1 supports 1 <= S <= ", tfsk::kAttnRaggedMaxSeq,
+                ", got S = ", S);
+    TORCH_CHECK(int64_t(S) * HD3 * 2 < (int64_t(1) << 31), "attention form 1: one image's qkv rows exceed 2 GiB");
+    TORCH_CHECK(aligned16(qkv), "attention form 1: qkv must be 16-byte aligned");
+  }
   const float* mb = nullptr;
   if (mask_bias.has_value()) {
     need(*mask_bias, at::kFloat, "mask_bias");
@@ -1073,9 +1080,34 @@ Tensor attention(const Tensor& qkv, const c10::optional<Tensor>& mask_bias, int6
   }
   Tensor y = out.has_value() ? *out : torch::empty({B, S, heads * D}, qkv.options());
   need(y, at::kBFloat16, "out");
+  TORCH_CHECK(y.numel() == int64_t(B) * S * heads * D, "out has the wrong size");
+  TORCH_CHECK(form == 0 || aligned16(y), "attention form 1: out must be 16-byte aligned");
   check(tfsk::attention_launch(bf16p(qkv), mb, bf16p_mut(y), B, S, heads, D, float(scale), mask_bstride,
-                               mask_qstride, cur_stream(qkv)),
+                               mask_qstride, int(form), cur_stream(qkv)),
         "attention");
+  return y;
+}
+
+// y[b, 0, :] = bf16(table[0, :]); y[b, 1 + p, :] = bf16(float(x[b, p, :]) + table[1 + p, :])
+// x: [B, P, C] bf16 (any leading shape with B * P * C elements per the arguments), table: [P + 1, C] f32
+Tensor patch_tokens(const Tensor& x, const Tensor& table, const c10::optional<Tensor>& out) {
+  need(x, at::kBFloat16, "x");
+  need(table, at::kFloat, "table");
+  TORCH_CHECK(x.dim() == 3, "patch_tokens: x must be [B, P, C]");
+  TORCH_CHECK(table.dim() == 2 && table.size(0) == x.size(1) + 1 && table.size(1) == x.size(2),
+              "patch_tokens: table must be [P + 1, C]");
+  const int64_t B = x.size(0), P = x.size(1), C = x.size(2);
+  TORCH_CHECK(C % 8 == 0, "patch_tokens: C % 8 != 0 (C = ", C, ")");
+  TORCH_CHECK(aligned16(x), "patch_tokens: x must be 16-byte aligned");
+  TORCH_CHECK(aligned16(table), "patch_tokens: table must be 16-byte aligned");
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
+  Tensor y = out.has_value() ? *out : torch::empty({B, P + 1, C}, x.options());
+  need(y, at::kBFloat16, "out");
+  TORCH_CHECK(y.numel() == B * (P + 1) * C, "patch_tokens: out has the wrong size");
+  TORCH_CHECK(aligned16(y), "patch_tokens: out must be 16-byte aligned");
+  TORCH_CHECK(tfsk::patch_tokens_supported(B, P, C), "patch_tokens: operands must be smaller than 2 GiB");
+  check(tfsk::patch_tokens_launch(bf16p(x), table.data_ptr<float>(), bf16p_mut(y), B, P, C, cur_stream(x)),
+        "patch_tokens");
   return y;
 }
 
@@ -1195,7 +1227,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "classifier_head that also stores its rows into pinned host memory when it runs as one launch: "
         "(probs, classes, wrote_host)");
   m.def("attention", &attention, py::arg("qkv"), py::arg("mask_bias"), py::arg("heads"), py::arg("scale"),
-        py::arg("out") = py::none(), py::arg("mask_bstride") = 0, py::arg("mask_qstride") = 0);
+        py::arg("out") = py::none(), py::arg("mask_bstride") = 0, py::arg("mask_qstride") = 0, py::arg("form") = 0,
+        "form 0: the fixed-S / KV-block kernels; form 1: the register kernel for any 1 <= S <= 256");
+  m.def("attention_forms", [](int64_t S) {
+    int forms[2];
+    const int k = tfsk::attention_forms(int(std::min<int64_t>(std::max<int64_t>(S, 0), 1 << 30)), forms);
+    return std::vector<int64_t>(forms, forms + k);
+  }, "the forms attention takes at length S: [0], or [0, 1] where the ragged register kernel applies");
+  m.def("patch_tokens", &patch_tokens, "class token + patches + position embedding in one launch",
+        py::arg("x"), py::arg("table"), py::arg("out") = py::none());
+  m.def("patch_tokens_supported", [](int64_t b, int64_t p, int64_t c) { return tfsk::patch_tokens_supported(b, p, c); },
+        "whether patch_tokens takes [B, P, C]: C % 8 == 0 and every operand below 2 GiB");
   m.def("splitk_counters_set_owner", [](int64_t owner) { tfsk::splitk_counters_set_owner(owner); },
         "tag the split-K counter slices this thread's captures take (0 = none)");
   m.def("splitk_counters_release", [](int64_t owner) { return tfsk::splitk_counters_release(owner); },

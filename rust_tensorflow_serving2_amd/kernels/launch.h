@@ -297,13 +297,33 @@ struct LnGemmArgs {
 };
 bool lngemm_supported(int M, int N, int K, int bm);
 hipError_t lngemm_launch(const LnGemmArgs& a, int bm, hipStream_t stream);
+// ViT front: y[b][0] = bf16(table[0]), y[b][1 + p] = bf16(float(x[b][p]) + table[1 + p]) over C columns
+// (x [B][P][C] bf16, table [P + 1][C] f32: row 0 = class token + pos[0], rows 1.. = pos[1..]);
+// C % 8 == 0, every operand 16-B aligned and below 2 GiB
+bool patch_tokens_supported(int64_t B, int64_t P, int64_t C);
+hipError_t patch_tokens_launch(const uint16_t* x, const float* table, uint16_t* y, int64_t B, int64_t P, int64_t C,
+                               hipStream_t stream);
 constexpr int kMaxAttentionSeq = 4096;
 // Fused multi-head attention over a packed QKV buffer [B*S][3*H*D] (bf16):
 // ctx[b,q,h,:] = softmax(Q K^T * scale + mask[b*bstride + q*qstride + key]) V
 // (additive f32 mask; strides 0 broadcast, e.g. BERT's [B,1,S,S] adder or a [B,S] key mask)
+// form 0: the fixed-S register kernel for S in {64, 128, 192, 256}, the KV-block
+// loop for any other S.  form 1 (kAttnFormRagged): the register kernel for any
+// 1 <= S <= kAttnRaggedMaxSeq at the padded length attention_ragged_sp(S);
+// hipErrorInvalidValue outside that range or for D != 64.
+constexpr int kAttnFormRagged = 1;
+constexpr int kAttnRaggedMaxSeq = 256;
+constexpr int attention_ragged_sp(int S) { return S <= 64 ? 64 : (S + 31) / 32 * 32; }
 hipError_t attention_launch(const uint16_t* qkv, const float* mask_bias, uint16_t* ctx, int B, int S,
-                            int H, int D, float scale, long mask_bstride, long mask_qstride,
+                            int H, int D, float scale, long mask_bstride, long mask_qstride, int form,
                             hipStream_t stream);
+// the forms attention_launch takes at length S (forms[0] = 0 always); returns the count (<= 2)
+inline int attention_forms(int S, int* forms) {
+  forms[0] = 0;
+  if (S < 1 || S > kAttnRaggedMaxSeq || (S % 64 == 0)) return 1;
+  forms[1] = kAttnFormRagged;
+  return 2;
+}
 // per-workgroup phase stamps of the following fixed-S attention launches
 // (entry, staged, softmax, P V, stored; [7] = CU id); nullptr: off
 void attention_set_trace(long long* trace, int cap);

@@ -448,6 +448,44 @@ __global__ void key_mask_adder_kernel(const void* __restrict__ m, int is_int, fl
   }
 }
 
+// ---------------------------------------------------------------- ViT patch tokens
+// Class token + patches + position embedding: one 16-B chunk of one output
+// token per thread, chunks fastest across lanes.  No branch around a load or a
+// store: the class row reads a clamped (in-range) x chunk and drops it by a
+// select -- never by a product, an Inf or NaN there must not reach the token
+// -- and the threads past the last chunk get kOOB offsets, which the
+// descriptors answer with zeros and drop on the store.
+__global__ __launch_bounds__(256) void patch_tokens_kernel(const uint16_t* __restrict__ x,
+                                                           const float* __restrict__ table,
+                                                           uint16_t* __restrict__ y, int B, int P, int CH) {
+  const int S = P + 1;
+  const long total = long(B) * S * CH;                        // output chunks (8 columns each)
+  const __amdgpu_buffer_rsrc_t rsX =
+      __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(x), 0, int(long(B) * P * CH * 16), 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsT =
+      __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(table), 0, int(long(S) * CH * 32), 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsY = __builtin_amdgcn_make_buffer_rsrc(y, 0, int(total * 16), 0x00020000);
+  const long i = long(blockIdx.x) * 256 + threadIdx.x;
+  const bool live = i < total;
+  const long tok = (live ? i : 0) / CH;                       // b * S + s
+  const int ch = int((live ? i : 0) - tok * CH);
+  const int b = int(tok / S), s = int(tok - long(b) * S);
+  const int p = s > 0 ? s - 1 : 0;                            // the class row reads patch 0 (dropped)
+  const uint32_t xoff = live ? uint32_t((long(b) * P + p) * CH + ch) * 16u : gemm::kOOB;
+  const uint32_t toff = live ? uint32_t(long(s) * CH + ch) * 32u : gemm::kOOB;
+  const u32x4 xv = __builtin_amdgcn_raw_buffer_load_b128(rsX, xoff, 0, 0);
+  const float4 t0 = gemm::buffer_f4(rsT, toff), t1 = gemm::buffer_f4(rsT, toff + 16u);
+  float f[8];
+  unpack8(make_uint4(xv.x, xv.y, xv.z, xv.w), f);
+  const float t[8] = {t0.x, t0.y, t0.z, t0.w, t1.x, t1.y, t1.z, t1.w};
+  float o[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) o[e] = (s > 0 ? f[e] : 0.f) + t[e];
+  const uint4 ov = pack8(o);
+  __builtin_amdgcn_raw_buffer_store_b128(u32x4{ov.x, ov.y, ov.z, ov.w}, rsY, live ? uint32_t(i) * 16u : gemm::kOOB, 0,
+                                         0);
+}
+
 // ---------------------------------------------------------------- LayerNorm
 // One wave per row, y = LN(x + r). Rows up to 64 * 8 * kLnChunks columns are
 // read once into registers (16-B loads), statistics are two-pass from the
@@ -1154,6 +1192,23 @@ hipError_t dense_softmax_launch(const float* x, int ldx, const uint16_t* w, int 
   if (N < 1 || N > kDsMaxN || K % 4 || ldx % 4 || ldw % 4) return hipErrorInvalidValue;
   if (rows == 0) return hipSuccess;
   hipLaunchKernelGGL(dense_softmax_kernel, dim3(rows), dim3(256), 0, s, x, ldx, w, ldw, bias, probs, N, K);
+  return hipGetLastError();
+}
+
+bool patch_tokens_supported(int64_t B, int64_t P, int64_t C) {
+  // byte counts and offsets are 32-bit in the descriptors: the largest operand is the fp32 table or y
+  const int64_t lim = int64_t(1) << 31;
+  return B >= 0 && P >= 1 && C >= 8 && C % 8 == 0 && B * (P + 1) * C * 2 < lim && (P + 1) * C * 4 < lim &&
+         (B * (P + 1) * (C / 8) + 255) / 256 < lim;
+}
+
+hipError_t patch_tokens_launch(const uint16_t* x, const float* table, uint16_t* y, int64_t B, int64_t P, int64_t C,
+                               hipStream_t s) {
+  if (!patch_tokens_supported(B, P, C)) return hipErrorInvalidValue;
+  const int64_t chunks = B * (P + 1) * (C / 8);
+  if (chunks == 0) return hipSuccess;
+  hipLaunchKernelGGL(patch_tokens_kernel, dim3(unsigned((chunks + 255) / 256)), dim3(256), 0, s, x, table, y, int(B),
+                     int(P), int(C / 8));
   return hipGetLastError();
 }
 

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """What does bf16 storage alone cost a MobileNet (or, with --family resnext, a
 ResNeXt-50 32x4d; with --family efficientnet, an EfficientNet-B0; with --family
-convnext, a ConvNeXt-T) end to end?  CPU only.
+convnext, a ConvNeXt-T; with --family vit, a ViT-S/16) end to end?  CPU only.
 
 Exports a random-init model, runs the fp32 interpreter, and runs the fused
 CPU program a second time with the conv weights rounded to bf16 and the output of
@@ -22,11 +22,15 @@ program stores -- with everything else in fp32.  Prints, per input seed:
 (V3_GATED_PROJECT_GAIN / V3_EXPAND_GAIN) for the exported model, or, with
 --family efficientnet, models/efficientnet.py's GATED_PROJECT_GAIN / EXPAND_GAIN.
 `--layer-scale` overrides models/convnext.py's LAYER_SCALE_INIT.
+`--vit-gains DENSE RESIDUAL QK` overrides models/vit.py's DENSE_GAIN, RESIDUAL_GAIN and QK_GAIN; with
+--family vit the GEMMs' bf16 outputs (everything but the fp32 head), the packed QKV, the attention
+output and the patch tokens are rounded as well, and --vit-config / --patch pick the model.
 
     python scripts/bf16_emulation.py --version v3_small --seeds 0 1 2 3 --trials 3
     python scripts/bf16_emulation.py --family resnext --seeds 3 4 --trials 1
     python scripts/bf16_emulation.py --family efficientnet --seeds 0 1 2 --trials 3
     python scripts/bf16_emulation.py --family convnext --seeds 0 1 2 --trials 3
+    python scripts/bf16_emulation.py --family vit --image-size 224 --seeds 0 1 2 --trials 2
 """
 import argparse
 import os
@@ -43,6 +47,7 @@ from rust_tensorflow_serving2_amd.server.servable import Servable, ServableOptio
 OUTS = ["classes", "probabilities"]
 ROUNDED = ("_FusedConv2D", "_FusedGroupedConv2D", "_FusedDepthwiseConv2D", "_SqueezeExcite", "_SqueezeExciteSigmoid",
            "_FusedDepthwiseLN", "_LayerNorm")
+VIT_ROUNDED = ROUNDED + ("_FusedMatMul", "_FusedQKV", "_Attention", "_PatchTokens")
 
 
 def bf16(t):
@@ -54,20 +59,22 @@ def centred_logits(probs):
     return lg - lg.mean(1, keepdims=True)
 
 
-def emulate(program, trial):
+def emulate(program, trial, ops=ROUNDED):
     """Round the fused ops' weights and outputs to bf16 in place; `trial[0]` selects the noise sample."""
     steps = []
-    for fn, node, ins, outs in program.steps:
-        if node.op in ROUNDED:
-            impl = node.attrs.get("_impl")
+    for step, (fn, node, ins, outs) in enumerate(program.steps):
+        impl = node.attrs.get("_impl")
+        if node.op in ops and not getattr(impl, "out_f32", False):
             if hasattr(impl, "w_ref"):
                 impl.w_ref = bf16(impl.w_ref)
 
-            def rounded(ctx, node, vals, fn=fn):
+            def rounded(ctx, node, vals, fn=fn, step=step):
                 res = []
                 for y in fn(ctx, node, vals):
                     if trial[0]:
-                        gen = torch.Generator().manual_seed(trial[0] * 1000 + len(res))
+                        # a pattern of its own per step: one pattern for every op would add up coherently
+                        # over layers of equal shape (a ViT's 12 blocks), which no summation order does
+                        gen = torch.Generator().manual_seed(trial[0] * 1000003 + step * 7 + len(res))
                         y = y * (1 + (torch.rand(y.shape, generator=gen) - 0.5) * 2.0 ** -9)
                     res.append(bf16(y))
                 return res
@@ -79,10 +86,11 @@ def emulate(program, trial):
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
-    ap.add_argument("--family", default="mobilenet", choices=["mobilenet", "resnext", "efficientnet", "convnext"],
+    ap.add_argument("--family", default="mobilenet", choices=["mobilenet", "resnext", "efficientnet", "convnext", "vit"],
                     help="resnext: ResNeXt-50 32x4d at full width (tests/test_resnext_gpu.py's model); efficientnet: "
                          "EfficientNet-B0 at full width (tests/test_efficientnet_gpu.py's model); convnext: ConvNeXt-T "
-                         "at full width and depth (tests/test_convnext_gpu.py's model); --version is MobileNet's")
+                         "at full width and depth (tests/test_convnext_gpu.py's model); vit: ViT-S/16 "
+                         "(tests/test_vit_gpu.py's model, at --image-size 224); --version is MobileNet's")
     ap.add_argument("--version", default="v3_small", choices=mobilenet.VERSIONS)
     ap.add_argument("--image-size", type=int, default=64)
     ap.add_argument("--model-seed", type=int, default=3)
@@ -92,6 +100,9 @@ def main():
     ap.add_argument("--gated-gain", type=float)
     ap.add_argument("--expand-gain", type=float)
     ap.add_argument("--layer-scale", type=float)
+    ap.add_argument("--vit-gains", type=float, nargs=3, metavar=("DENSE", "RESIDUAL", "QK"))
+    ap.add_argument("--vit-config", default="vit_small")
+    ap.add_argument("--patch", type=int, default=16)
     a = ap.parse_args()
     if a.gated_gain is not None:
         mobilenet.V3_GATED_PROJECT_GAIN = dict(mobilenet.V3_GATED_PROJECT_GAIN, **{a.version: a.gated_gain})
@@ -111,6 +122,11 @@ def main():
         if a.layer_scale is not None:
             convnext.LAYER_SCALE_INIT = a.layer_scale
         print(a.version, "layer scale init", convnext.LAYER_SCALE_INIT)
+    elif a.family == "vit":
+        from rust_tensorflow_serving2_amd.models import vit
+        a.version = f"{a.vit_config}/{a.patch}"
+        gains = tuple(a.vit_gains) if a.vit_gains else (vit.DENSE_GAIN, vit.RESIDUAL_GAIN, vit.QK_GAIN)
+        print(a.version, "dense / residual / qk gains", gains)
     elif a.family == "resnext":
         a.version = "resnext50"
     elif a.version.startswith("v3"):
@@ -121,6 +137,8 @@ def main():
         efficientnet.export(path, image_size=a.image_size, seed=a.model_seed)
     elif a.family == "convnext":
         convnext.export(path, image_size=a.image_size, seed=a.model_seed, layer_scale_init=convnext.LAYER_SCALE_INIT)
+    elif a.family == "vit":
+        vit.export(path, config=a.vit_config, patch=a.patch, image_size=a.image_size, seed=a.model_seed, gains=gains)
     elif a.family == "resnext":
         from rust_tensorflow_serving2_amd.models import resnet
         resnet.export(path, groups=32, width_per_group=4, image_size=a.image_size, seed=a.model_seed)
@@ -129,7 +147,7 @@ def main():
     ref = Servable("m", 1, path, ServableOptions(device="cpu"))
     emu = Servable("m", 1, path, ServableOptions(device="cpu", fuse=True))
     trial = [0]
-    emulate(emu.runner("serving_default", ["input"], OUTS).program, trial)
+    emulate(emu.runner("serving_default", ["input"], OUTS).program, trial, VIT_ROUNDED if a.family == "vit" else ROUNDED)
     np.set_printoptions(precision=4, suppress=True)
     for s in a.seeds:
         x = np.random.default_rng(s).random((a.batch, a.image_size, a.image_size, 3), dtype=np.float32)

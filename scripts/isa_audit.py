@@ -146,6 +146,9 @@ def resources(asm: str):
     for sym, body in kernels(asm):
         code = [ln.split(";")[0].strip() for ln in body]
         code = [ln for ln in code if ln and not ln.startswith(".")]
+        # a branch target names the function's index in its file (.LBB<fn>_<block>): masked, so a
+        # kernel added above another one does not move the other's digest
+        code = [re.sub(r"\.LBB\d+_", ".LBB_", ln) for ln in code]
         out[sym] = {"mfma": sum(bool(MFMA.match(ln)) for ln in code),
                     "code": hashlib.sha1("\n".join(code).encode()).hexdigest()[:12]}
     cur = meta = None
