@@ -33,6 +33,8 @@ a single consumer and is not fetched):
   known multiple of the filter's in-depth channels (a grouped conv: ResNeXt)
   => ``_FusedGroupedConv2D``: BN folded, one ``gconv2d`` launch (kernels/gconv.hip)
   for 3x3 filters with 4 / 8 / 16 / 32 channels per group.
+  (The dense, depthwise and grouped patterns share their head, ``[Pad] -> conv ->
+  [BiasAdd] -> [FusedBatchNorm*]`` and its guards: ``_match_conv_chain``.)
 * ``MatMul -> [BiasAdd] -> [Add(residual)] -> [Relu|Tanh|GELU]`` => ``_FusedMatMul``
   (fp32 output when it feeds a Softmax/ArgMax head or is fetched).
 * ``Mean(NHWC, axes=[1,2])`` => ``_GlobalAvgPool``;  ``MaxPool`` => ``_MaxPool``;
@@ -193,16 +195,52 @@ def _to_bf16(x: torch.Tensor) -> torch.Tensor:
 
 
 # ------------------------------------------------------------------ fused op impls
-class FusedConv:
+class _Window:
+    """The kh x kw window, stride (sh, sw), that the conv and pool ops slide over
+    H and W of an NHWC tensor.  Methods and plain fields only: the tensors of an
+    op are its own (placement.weight_refs lays them out by attribute name)."""
+
+    def _set_window(self, kh: int, kw: int, strides, padding: str, pads):
+        self.kh, self.kw = kh, kw
+        self.sh, self.sw = strides
+        self.padding = padding          # "SAME" | "VALID" | "EXPLICIT"
+        self.pads = pads                # (pt, pb, pl, pr) for EXPLICIT
+
+    def pads_for(self, h, w):
+        if self.padding == "SAME":
+            return O.tf_same_pads(h, self.kh, self.sh) + O.tf_same_pads(w, self.kw, self.sw)
+        if self.padding == "EXPLICIT":
+            return tuple(self.pads)
+        return (0, 0, 0, 0)
+
+    def out_hw(self, h, w, pads, kh=None, kw=None):
+        """(ho, wo) of an h x w input under ``pads``; ``kh`` / ``kw`` stand in
+        for the window's own extent (FusedConv's padded RGBA filter)."""
+        pt, pb, pl, pr = pads
+        kh, kw = self.kh if kh is None else kh, self.kw if kw is None else kw
+        return (h + pt + pb - kh) // self.sh + 1, (w + pl + pr - kw) // self.sw + 1
+
+
+def _grouped_conv_torch(x: torch.Tensor, w_hwio: torch.Tensor, bias: torch.Tensor, strides, pads, groups: int):
+    """NHWC ``conv2d(pad(x), w, groups=) + bias`` in the dtype of ``x`` (the
+    interpreter's Conv2D, ops._conv2d: the same calls, so the same errors).
+    The one reference conv of the fused ops: dense is ``groups`` 1, depthwise
+    ``groups`` C with the filter as [kh, kw, 1, C]."""
+    pt, pb, pl, pr = pads
+    xc = x.permute(0, 3, 1, 2)
+    xc = F.pad(xc, [pl, pr, pt, pb]) if (pt or pb or pl or pr) else xc
+    y = F.conv2d(xc, w_hwio.to(x.dtype).permute(3, 2, 0, 1), stride=tuple(strides), groups=groups)
+    return y.permute(0, 2, 3, 1) + bias.to(x.dtype)
+
+
+class FusedConv(_Window):
     """Conv2D(+folded BN/bias)(+residual)(+act).  Weights: HWIO fp32 (reference)
     and [Cout][Kpad] bf16 (kernel)."""
 
     def __init__(self, w_hwio: torch.Tensor, bias: torch.Tensor, strides, padding: str, pads, act: str,
                  device: torch.device, use_hip: bool, name: str):
-        self.kh, self.kw, self.cin, self.cout = w_hwio.shape
-        self.sh, self.sw = strides
-        self.padding = padding          # "SAME" | "VALID" | "EXPLICIT"
-        self.pads = pads                # (pt, pb, pl, pr) for EXPLICIT
+        kh, kw, self.cin, self.cout = w_hwio.shape
+        self._set_window(kh, kw, strides, padding, pads)
         self.act = act
         self.use_hip = use_hip
         self.name = name
@@ -243,13 +281,6 @@ class FusedConv:
                                     self.act not in IGEMM_ONLY_ACTS)   # (the post output is cgemm / halo only; they
         #                                                                  have no relu6 / hard_swish)
 
-    def pads_for(self, h, w):
-        if self.padding == "SAME":
-            return O.tf_same_pads(h, self.kh, self.sh) + O.tf_same_pads(w, self.kw, self.sw)
-        if self.padding == "EXPLICIT":
-            return tuple(self.pads)
-        return (0, 0, 0, 0)
-
     def _hwio(self) -> torch.Tensor:
         """The folded filter as fp32 HWIO, from whichever form this op keeps."""
         if not self.use_hip:
@@ -260,15 +291,15 @@ class FusedConv:
             w = self.w[:, :self.kh * self.kw * self.cin].reshape(self.cout, self.kh, self.kw, self.cin)
         return w.float().permute(1, 2, 3, 0)
 
-    def _other_depth(self, x, res, pads):
-        """The input has another channel count than the filter's in-depth (the
-        pass could not see it): Conv2D's own semantics with torch -- a grouped
-        conv when the counts divide, else torch's error, which the executor
-        reports as the interpreter's Conv2D does."""
-        pt, pb, pl, pr = pads
+    def _torch(self, x, res, pads):
+        """The fp32 reference (the CPU path), and on the device an input with
+        another channel count than the filter's in-depth (the pass could not
+        see it): Conv2D's own semantics with torch -- a grouped conv when the
+        counts divide, else torch's error, which the executor reports as the
+        interpreter's Conv2D does."""
         w = self._hwio().to(x.device)
         b = (self.b if self.use_hip else self.b_ref).to(x.device)
-        y = _grouped_conv_torch(x.float(), w, b, (self.sh, self.sw), (pt, pb, pl, pr), x.shape[3] // self.cin)
+        y = _grouped_conv_torch(x.float(), w, b, (self.sh, self.sw), pads, x.shape[3] // self.cin)
         if res is not None:
             y = y + res.float()
         outs = _with_post(self, _ref_act(y, self.act).contiguous())
@@ -278,22 +309,13 @@ class FusedConv:
         x = O.to_torch(ins[0])
         res = O.to_torch(ins[1]) if len(ins) > 1 else None
         pt, pb, pl, pr = self.pads_for(x.shape[1], x.shape[2])
-        if x.shape[3] != self.cin:
-            return self._other_depth(x, res, (pt, pb, pl, pr))
-        if not self.use_hip:
-            y = F.conv2d(F.pad(x.float().permute(0, 3, 1, 2), [pl, pr, pt, pb]),
-                         self.w_ref.permute(3, 2, 0, 1), stride=(self.sh, self.sw))
-            y = y.permute(0, 2, 3, 1) + self.b_ref
-            if res is not None:
-                y = y + res.float()
-            return _with_post(self, _ref_act(y, self.act).contiguous())
+        if not self.use_hip or x.shape[3] != self.cin:
+            return self._torch(x, res, (pt, pb, pl, pr))
         from ..ops import ACT, hip, tuned_config
         if self.c4:
             # fp32 RGB request -> zero-bordered bf16 RGBA sized for the padded
             # (khp x 8) filter; the conv itself then has no padding
-            h, w = x.shape[1], x.shape[2]
-            ho = (h + pt + pb - self.kh) // self.sh + 1
-            wo = (w + pl + pr - self.kw) // self.sw + 1
+            ho, wo = self.out_hw(x.shape[1], x.shape[2], (pt, pb, pl, pr))
             hp, wp = (ho - 1) * self.sh + self.khp, (wo - 1) * self.sw + 8
             x = hip().ingest_c4_padded(x.float().contiguous(), hp, wp, pt, pl)
             pt = pb = pl = pr = 0
@@ -304,8 +326,7 @@ class FusedConv:
         H = hip()
         n, h, w, _ = x.shape
         kh, kw = (self.khp, 8) if self.c4 else (self.kh, self.kw)
-        ho = (h + pt + pb - kh) // self.sh + 1
-        wo = (w + pl + pr - kw) // self.sw + 1
+        ho, wo = self.out_hw(h, w, (pt, pb, pl, pr), kh, kw)
         if res is not None:
             # the kernel reads one residual element per output element: a broadcast operand
             # ([B,1,1,C], [1,1,1,C], a scalar) is expanded first
@@ -340,7 +361,7 @@ class FusedConv:
         return outs
 
 
-class FusedDepthwiseConv:
+class FusedDepthwiseConv(_Window):
     """DepthwiseConv2dNative (channel multiplier 1)(+folded BN/bias)(+act).
     The filter stays fp32 on both paths: [KH][KW][C], which the kernel reads as
     [KH*KW][C] (9 C floats for a 3x3: rounding it to bf16 would cost 2^-9
@@ -350,10 +371,8 @@ class FusedDepthwiseConv:
 
     def __init__(self, w_hwc: torch.Tensor, bias: torch.Tensor, strides, padding: str, pads, act: str,
                  device: torch.device, use_hip: bool, name: str):
-        self.kh, self.kw, self.c = w_hwc.shape
-        self.sh, self.sw = strides
-        self.padding = padding          # "SAME" | "VALID" | "EXPLICIT"
-        self.pads = pads                # (pt, pb, pl, pr) for EXPLICIT
+        kh, kw, self.c = w_hwc.shape
+        self._set_window(kh, kw, strides, padding, pads)
         self.act = act
         self.use_hip = use_hip
         self.name = name
@@ -365,20 +384,18 @@ class FusedDepthwiseConv:
     def hip_ok(cls, kh: int, kw: int, c: int) -> bool:
         return c % 8 == 0 and kh <= cls.MAX_K and kw <= cls.MAX_K
 
-    pads_for = FusedConv.pads_for
+    def _torch(self, x, pads):
+        """The fp32 reference conv (no activation): the filter as [kh, kw, 1, C], C groups."""
+        w = self.w.to(x.device).reshape(self.kh, self.kw, 1, self.c)
+        return _grouped_conv_torch(x.float(), w, self.b.to(x.device), (self.sh, self.sw), pads, self.c)
 
     def __call__(self, ctx, node, ins):
         x = O.to_torch(ins[0])
         pt, pb, pl, pr = self.pads_for(x.shape[1], x.shape[2])
         n, h, w, _ = x.shape
-        ho = (h + pt + pb - self.kh) // self.sh + 1
-        wo = (w + pl + pr - self.kw) // self.sw + 1
+        ho, wo = self.out_hw(h, w, (pt, pb, pl, pr))
         if not self.use_hip:
-            wt = self.w.to(x.device).permute(2, 0, 1).reshape(self.c, 1, self.kh, self.kw)
-            y = F.conv2d(F.pad(x.float().permute(0, 3, 1, 2), [pl, pr, pt, pb]), wt, stride=(self.sh, self.sw),
-                         groups=self.c)
-            y = y.permute(0, 2, 3, 1) + self.b.to(x.device)
-            return [_ref_act(y, self.act).contiguous()]
+            return [_ref_act(self._torch(x, (pt, pb, pl, pr)), self.act).contiguous()]
         from ..ops import ACT, hip, tuned_choice
         H = hip()
         x = _to_bf16(x).contiguous()
@@ -436,12 +453,10 @@ class FusedDepthwiseLN:
         dw = self.dw
         pt, pb, pl, pr = dw.pads_for(x.shape[1], x.shape[2])
         n, h, w, _ = x.shape
-        ho, wo = h + pt + pb - 6, w + pl + pr - 6
+        ho, wo = dw.out_hw(h, w, (pt, pb, pl, pr))
         gamma, beta = self.ln.params(self.c)
         if not self.use_hip:
-            wt = dw.w.to(x.device).permute(2, 0, 1).reshape(self.c, 1, 7, 7)
-            y = F.conv2d(F.pad(x.float().permute(0, 3, 1, 2), [pl, pr, pt, pb]), wt, groups=self.c)
-            y = y.permute(0, 2, 3, 1) + dw.b.to(x.device)
+            y = dw._torch(x, (pt, pb, pl, pr))
             return [F.layer_norm(y, (self.c,), gamma.to(x.device), beta.to(x.device), self.eps).contiguous()]
         from ..ops import hip
         H = hip()
@@ -451,16 +466,6 @@ class FusedDepthwiseLN:
         x = _to_bf16(x).contiguous()
         out = torch.empty((n, ho, wo, self.c), device=x.device, dtype=BF16)
         return [H.dwconv_ln(x, dw.w, dw.b, gamma, beta, self.eps, pt, pl, ho, wo, out)]
-
-
-def _grouped_conv_torch(x: torch.Tensor, w_hwio: torch.Tensor, bias: torch.Tensor, strides, pads, groups: int):
-    """NHWC ``conv2d(pad(x), w, groups=) + bias`` in the dtype of ``x`` (the
-    interpreter's Conv2D, ops._conv2d: the same calls, so the same errors)."""
-    pt, pb, pl, pr = pads
-    xc = x.permute(0, 3, 1, 2)
-    xc = F.pad(xc, [pl, pr, pt, pb]) if (pt or pb or pl or pr) else xc
-    y = F.conv2d(xc, w_hwio.to(x.dtype).permute(3, 2, 0, 1), stride=tuple(strides), groups=groups)
-    return y.permute(0, 2, 3, 1) + bias.to(x.dtype)
 
 
 GCONV_CG = (4, 8, 16, 32)         # kernels/gconv.hip: channels per group, in == out
@@ -487,7 +492,7 @@ def pack_grouped_filter(w_hwio: torch.Tensor, cg: int) -> torch.Tensor:
     return b.contiguous().to(BF16).reshape(-1)
 
 
-class FusedGroupedConv:
+class FusedGroupedConv(_Window):
     """Grouped Conv2D (a filter whose in-depth is C / groups)(+folded BN/bias)(+act
     none | relu).  The fp32 HWIO filter serves the CPU reference and the torch
     paths; the kernel (kernels/gconv.hip: 3x3, equal strides 1 | 2, cg inputs
@@ -496,13 +501,11 @@ class FusedGroupedConv:
 
     def __init__(self, w_hwio: torch.Tensor, bias: torch.Tensor, strides, padding: str, pads, act: str,
                  device: torch.device, use_hip: bool, name: str, channels: int):
-        self.kh, self.kw, self.cg, self.cout = w_hwio.shape
+        kh, kw, self.cg, self.cout = w_hwio.shape
+        self._set_window(kh, kw, strides, padding, pads)
         self.c = channels                           # input channels the pass saw: groups * cg
         self.groups = channels // self.cg
         self.cgo = self.cout // self.groups
-        self.sh, self.sw = strides
-        self.padding = padding          # "SAME" | "VALID" | "EXPLICIT"
-        self.pads = pads                # (pt, pb, pl, pr) for EXPLICIT
         self.act = act
         self.use_hip = use_hip
         self.name = name
@@ -519,8 +522,6 @@ class FusedGroupedConv:
         """What kernels/gconv.hip takes (launch.h gconv_supported)."""
         return (kh == 3 and kw == 3 and cg_in == cg_out and cg_in in GCONV_CG and c % 8 == 0 and c % cg_in == 0 and
                 strides[0] == strides[1] and strides[0] in (1, 2))
-
-    pads_for = FusedConv.pads_for
 
     def _hwio(self) -> torch.Tensor:
         if hasattr(self, "w_ref"):
@@ -545,10 +546,9 @@ class FusedGroupedConv:
         if not self.kernel or x.shape[3] != self.c or os.environ.get("TFSERVE_GCONV", "1") == "0":
             return self._torch(x, pads)
         from ..ops import ACT, hip
-        pt, pb, pl, pr = pads
+        pt, _pb, pl, _pr = pads
         n, h, w, _ = x.shape
-        ho = (h + pt + pb - 3) // self.sh + 1
-        wo = (w + pl + pr - 3) // self.sh + 1
+        ho, wo = self.out_hw(h, w, pads)
         x = _to_bf16(x).contiguous()
         out = torch.empty((n, ho, wo, self.cout), device=x.device, dtype=BF16)
         return [hip().gconv2d(x, self.w, self.b, self.cg, self.sh, pt, pl, ho, wo, ACT[self.act], out)]
@@ -1090,17 +1090,12 @@ class GlobalAvgPool:
         return [y.reshape(y.shape[0], 1, 1, -1) if self.keep else y]
 
 
-class MaxPool:
+class MaxPool(_Window):
     def __init__(self, ksize, strides, padding, use_hip, pads=(0, 0, 0, 0)):
-        self.kh, self.kw = ksize
-        self.sh, self.sw = strides
-        self.padding = padding          # "SAME" | "VALID" | "EXPLICIT"
-        self.pads = tuple(pads)         # (pt, pb, pl, pr) for EXPLICIT
+        self._set_window(*ksize, strides, padding, tuple(pads))
         self.use_hip = use_hip
         self.post = None
         self.post_mode = None
-
-    pads_for = FusedConv.pads_for
 
     def set_post(self, scale, shift, act, mode, device=None):
         # on the device up front: a host->device copy inside HIP-graph capture is illegal
@@ -1225,8 +1220,7 @@ class StemPool:
             return pool(ctx, node, conv(ctx, node, [x]))
         from ..ops import ACT, hip
         pt, pb, pl, pr = conv.pads_for(x.shape[1], x.shape[2])
-        hc = (x.shape[1] + pt + pb - conv.kh) // conv.sh + 1
-        wc = (x.shape[2] + pl + pr - conv.kw) // conv.sw + 1
+        hc, wc = conv.out_hw(x.shape[1], x.shape[2], (pt, pb, pl, pr))
         ppt, ppb, ppl, ppr = pool.pads_for(hc, wc)
         kw = {}
         if pool.post is not None:
@@ -1500,13 +1494,115 @@ def _absorb_pad(g: Graph, c: _Ctx, n: Node, x_ref, padding: str, pads, chain: Li
     return x_ref, padding, pads
 
 
+class _ConvChain:
+    """What ``_match_conv_chain`` found: the conv's input and padding, the fp32
+    filter and bias with everything so far folded in, and a cursor -- the nodes
+    taken (``chain``, which ``_finalize`` deletes) and the node at the end
+    (``cur``).  The passes move the cursor on over what only they absorb."""
+
+    def __init__(self, c: _Ctx, x_ref, padding: str, pads, strides, w, bias, chain: List[Node]):
+        self.c, self.x_ref, self.padding, self.pads, self.strides = c, x_ref, padding, pads, strides
+        self.w, self.bias, self.act = w, bias, "none"
+        self.chain, self.cur = chain, chain[-1]
+
+    @property
+    def nxt(self) -> Optional[Node]:
+        """The only reader of output 0 of ``cur``, when ``cur`` is not fetched."""
+        return self.c.only_consumer(self.cur.name)
+
+    def take(self, *nodes: Node) -> Optional[Node]:
+        """Append ``nodes`` (the last one is the new ``cur``); returns the new ``nxt``."""
+        self.chain += nodes
+        self.cur = nodes[-1]
+        return self.nxt
+
+    def close(self, acts: Dict[str, str]):
+        """Take ``nxt`` as the closing activation if its op is one of ``acts`` (op -> the kernels' name)."""
+        nxt = self.nxt
+        if nxt is not None and nxt.op in acts:
+            self.act = acts[nxt.op]
+            self.take(nxt)
+
+
+def _match_conv_chain(g: Graph, c: _Ctx, n: Node, accept) -> Optional[_ConvChain]:
+    """The head the conv passes share, from the ``Conv2D`` / ``DepthwiseConv2dNative``
+    node ``n``: ``[Pad ->] n [-> BiasAdd] [-> FusedBatchNorm*]``, or None.
+
+    Guards: NHWC, dilation 1, a constant 4-D filter, ``EXPLICIT`` paddings with
+    zero batch and channel entries.  ``accept(filter)`` holds the calling pass's
+    own conditions: it returns the filter as the pass's op takes it, output
+    channels last, or None to leave the conv alone.  A spatial ``Pad`` read only
+    by ``n`` becomes explicit padding; a ``BiasAdd`` of a constant ``(cout,)``
+    and an inference BatchNorm with ``cout`` elements (``_bn_affine``) are folded
+    as ``w *= scale; bias = bias * scale + shift`` -- tensor arithmetic only, so
+    that shape-only (meta) weights fold too."""
+    if n.sattr("data_format", "NHWC") != "NHWC":
+        return None
+    dil = n.attr("dilations", [1, 1, 1, 1]) or [1, 1, 1, 1]
+    if any(d != 1 for d in dil):
+        return None
+    w = _const(g, n.inputs[1])
+    w = accept(w) if w is not None and w.dim() == 4 else None
+    if w is None:
+        return None
+    padding = n.sattr("padding", "VALID")
+    pads = (0, 0, 0, 0)
+    chain: List[Node] = []
+    if padding == "EXPLICIT":
+        ep = n.attr("explicit_paddings", [])
+        if ep[0] or ep[1] or ep[6] or ep[7]:
+            return None
+        pads = (ep[2], ep[3], ep[4], ep[5])
+    x_ref, padding, pads = _absorb_pad(g, c, n, n.inputs[0], padding, pads, chain)
+    strides = n.attr("strides", [1, 1, 1, 1])
+    w = w.float()
+    cout = w.shape[-1]
+    m = _ConvChain(c, x_ref, padding, pads, (strides[1], strides[2]), w, zeros(cout, w), chain + [n])
+    nxt = m.nxt
+    if nxt is not None and nxt.op == "BiasAdd" and nxt.inputs[0] == (m.cur.name, 0):
+        b = _const(g, nxt.inputs[1])
+        if b is not None and tuple(b.shape) == (cout,):
+            m.bias = m.bias + b.float()
+            nxt = m.take(nxt)
+    if nxt is not None and nxt.op in _BATCH_NORMS and nxt.inputs[0] == (m.cur.name, 0):
+        aff = _bn_affine(g, c, nxt)
+        if aff is not None and aff[0].numel() == cout:
+            m.w = m.w * aff[0]
+            m.bias = m.bias * aff[0] + aff[1]
+            m.take(nxt)
+    return m
+
+
+def _bn_affine(g: Graph, c: _Ctx, bn: Node):
+    """(scale, shift) of an inference FusedBatchNorm with constant params whose
+    only used output is y, else None."""
+    if bn.op not in _BATCH_NORMS or bn.attr("is_training", False) \
+            or bn.sattr("data_format", "NHWC") != "NHWC" or bn.name in c.fetch_nodes:
+        return None
+    params = [_const(g, r) for r in bn.inputs[1:5]]
+    if any(p is None for p in params) or {i for _c, _p, i in c.cons.get(bn.name, [])} - {0}:
+        return None
+    gamma, beta, mean, var = (p.float().reshape(-1) for p in params)
+    scale = gamma * torch.rsqrt(var + float(bn.attr("epsilon", 1e-3)))
+    return scale, beta - mean * scale
+
+
+def _group_channels(g: Graph, n: Node, fed, w: torch.Tensor) -> Optional[int]:
+    """The input channel count the graph declares for ``Conv2D`` ``n`` where it
+    makes ``n`` a grouped conv -- a proper multiple of the filter's in-depth,
+    which is above 1, with the outputs dividing among the groups -- else None."""
+    cg, cout = int(w.shape[2]), int(w.shape[3])
+    ch = _channels_of(g, n.inputs[0], fed) if cg > 1 else None
+    return None if ch is None or ch == cg or ch % cg or cout % (ch // cg) else ch
+
+
 def fuse_grouped_conv(g, order, fed, fetch_refs, device, opts):
     """``[Pad ->] Conv2D [-> BiasAdd] [-> FusedBatchNorm*] [-> Relu]`` ->
     ``_FusedGroupedConv2D`` where the conv is a GROUPED one: the channel count
     of its input (``_channels_of``) is known and a proper multiple of the
     filter's in-depth, which is above 1 (in-depth 1 is a depthwise conv spelled
-    as Conv2D: it stays on the reference op).  fuse_conv's guards apply (NHWC,
-    dilation 1, a constant 4-D filter, an inference BatchNorm whose only used
+    as Conv2D: it stays on the reference op).  ``_match_conv_chain``'s guards apply
+    (NHWC, dilation 1, a constant 4-D filter, an inference BatchNorm whose only used
     output is y, no fetch inside the chain, single consumers).  No residual
     ``Add`` is absorbed (the kernel reads none), and a closing activation other
     than Relu stays a node of its own.  3x3 filters with 4 / 8 / 16 / 32
@@ -1522,228 +1618,91 @@ def fuse_grouped_conv(g, order, fed, fetch_refs, device, opts):
     c = _Ctx(g, order, fed, fetch_refs, device, opts)
     for name in order:
         n = g.nodes.get(name)
-        if n is None or n.op != "Conv2D" or n.sattr("data_format", "NHWC") != "NHWC":
+        if n is None or n.op != "Conv2D":
             continue
-        dil = n.attr("dilations", [1, 1, 1, 1]) or [1, 1, 1, 1]
-        if any(d != 1 for d in dil):
+        m = _match_conv_chain(g, c, n, lambda w: w if _group_channels(g, n, fed, w) else None)
+        if m is None:
             continue
-        w = _const(g, n.inputs[1])
-        if w is None or w.dim() != 4 or w.shape[2] <= 1:
-            continue
-        cg, cout = int(w.shape[2]), int(w.shape[3])
-        ch = _channels_of(g, n.inputs[0], fed)
-        if ch is None or ch == cg or ch % cg or cout % (ch // cg):
-            continue
-        padding = n.sattr("padding", "VALID")
-        pads = (0, 0, 0, 0)
-        chain: List[Node] = []
-        if padding == "EXPLICIT":
-            ep = n.attr("explicit_paddings", [])
-            if ep[0] or ep[1] or ep[6] or ep[7]:
-                continue
-            pads = (ep[2], ep[3], ep[4], ep[5])
-        x_ref, padding, pads = _absorb_pad(g, c, n, n.inputs[0], padding, pads, chain)
-        strides = n.attr("strides", [1, 1, 1, 1])
-        w = w.float()
-        bias = zeros(cout, w)
-        chain.append(n)
-        cur = n
-        act = "none"
-        nxt = c.only_consumer(cur.name)
-        if nxt is not None and nxt.op == "BiasAdd" and nxt.inputs[0] == (cur.name, 0):
-            b = _const(g, nxt.inputs[1])
-            if b is not None and tuple(b.shape) == (cout,):
-                bias = bias + b.float()
-                chain.append(nxt)
-                cur = nxt
-                nxt = c.only_consumer(cur.name)
-        if nxt is not None and nxt.op in _BATCH_NORMS and nxt.inputs[0] == (cur.name, 0):
-            aff = _bn_affine(g, c, nxt)
-            if aff is not None and aff[0].numel() == cout:
-                w = w * aff[0]
-                bias = bias * aff[0] + aff[1]
-                chain.append(nxt)
-                cur = nxt
-                nxt = c.only_consumer(cur.name)
-        if nxt is not None and nxt.op == "Relu":
-            act = "relu"
-            chain.append(nxt)
-            cur = nxt
-        impl = FusedGroupedConv(w, bias, (strides[1], strides[2]), padding, pads, act, device, c.use_hip, cur.name, ch)
-        _finalize(g, chain, "_FusedGroupedConv2D", [x_ref], {"_impl": impl})
+        m.close({"Relu": "relu"})
+        impl = FusedGroupedConv(m.w, m.bias, m.strides, m.padding, m.pads, m.act, device, c.use_hip, m.cur.name,
+                                _group_channels(g, n, fed, m.w))
+        _finalize(g, m.chain, "_FusedGroupedConv2D", [m.x_ref], {"_impl": impl})
         c.refresh()
 
 
 def fuse_conv(g, order, fed, fetch_refs, device, opts):
+    """``_match_conv_chain``'s head ``[-> Mul(const [C])] [-> Add(residual)] [-> GELU subgraph | Relu | Relu6 |
+    _HardSwish | _Swish]`` -> ``_FusedConv2D`` for a dense ``Conv2D``."""
     c = _Ctx(g, order, fed, fetch_refs, device, opts)
     for name in order:
         n = g.nodes.get(name)
-        if n is None or n.op != "Conv2D" or n.sattr("data_format", "NHWC") != "NHWC":
+        if n is None or n.op != "Conv2D":
             continue
-        dil = n.attr("dilations", [1, 1, 1, 1]) or [1, 1, 1, 1]
-        if any(d != 1 for d in dil):
+
+        def dense(w):
+            # a grouped conv (Conv2D has no groups attribute: its input has more channels than the filter's
+            # in-depth) is fuse_grouped_conv's, or stays on the reference op; an input whose channel count
+            # the graph does not tell is checked by FusedConv when it runs
+            return w if _channels_of(g, n.inputs[0], fed) in (None, int(w.shape[2])) else None
+        m = _match_conv_chain(g, c, n, dense)
+        if m is None:
             continue
-        w = _const(g, n.inputs[1])
-        if w is None or w.dim() != 4:
-            continue
-        # a grouped conv (Conv2D has no groups attribute: its input has more channels than the filter's
-        # in-depth) is fuse_grouped_conv's, or stays on the reference op; an input whose channel count
-        # the graph does not tell is checked by FusedConv when it runs
-        if _channels_of(g, n.inputs[0], fed) not in (None, int(w.shape[2])):
-            continue
-        x_ref = n.inputs[0]
-        padding = n.sattr("padding", "VALID")
-        pads = (0, 0, 0, 0)
-        chain: List[Node] = []
-        if padding == "EXPLICIT":
-            ep = n.attr("explicit_paddings", [])
-            if ep[0] or ep[1] or ep[6] or ep[7]:
-                continue
-            pads = (ep[2], ep[3], ep[4], ep[5])
-        prod = g.nodes.get(x_ref[0])
-        if (padding == "VALID" and prod is not None and prod.op == "Pad" and x_ref[1] == 0
-                and c.only_consumer(prod.name) is n):
-            pv = _const(g, prod.inputs[1])
-            if pv is not None:
-                p = [int(v) for v in pv.reshape(-1).tolist()]
-                if len(p) == 8 and p[0] == p[1] == p[6] == p[7] == 0 and min(p) >= 0:
-                    chain.append(prod)
-                    x_ref = prod.inputs[0]
-                    padding, pads = "EXPLICIT", (p[2], p[3], p[4], p[5])
-        strides = n.attr("strides", [1, 1, 1, 1])
-        w = w.float()
-        cout = w.shape[3]
-        bias = zeros(cout, w)
-        chain.append(n)
-        cur = n
+        cout = m.w.shape[3]
         residual = None
-        act = "none"
-        nxt = c.only_consumer(cur.name)
-        if nxt is not None and nxt.op == "BiasAdd" and nxt.inputs[0] == (cur.name, 0):
-            b = _const(g, nxt.inputs[1])
-            if b is not None and tuple(b.shape) == (cout,):
-                bias = bias + b.float()
-                chain.append(nxt)
-                cur = nxt
-                nxt = c.only_consumer(cur.name)
-        if (nxt is not None and nxt.op in ("FusedBatchNorm", "FusedBatchNormV2", "FusedBatchNormV3")
-                and not nxt.attr("is_training", False) and nxt.sattr("data_format", "NHWC") == "NHWC"
-                and nxt.inputs[0] == (cur.name, 0)):
-            params = [_const(g, r) for r in nxt.inputs[1:5]]
-            outs_used = {i for _c, _p, i in c.cons.get(nxt.name, [])}
-            if all(p is not None for p in params) and outs_used <= {0} and nxt.name not in c.fetch_nodes:
-                gamma, beta, mean, var = (p.float() for p in params)
-                scale = gamma * torch.rsqrt(var + float(nxt.attr("epsilon", 1e-3)))
-                w = w * scale
-                bias = (bias - mean) * scale + beta
-                chain.append(nxt)
-                cur = nxt
-                nxt = c.only_consumer(cur.name)
+        nxt = m.nxt
         # a constant per-channel / scalar scale (ResNet v2's residual scale):
         # folded into the weights and bias
-        if nxt is not None and nxt.op == "Mul" and len(nxt.inputs) == 2 and (cur.name, 0) in nxt.inputs:
-            other = nxt.inputs[1] if nxt.inputs[0] == (cur.name, 0) else nxt.inputs[0]
+        if nxt is not None and nxt.op == "Mul" and len(nxt.inputs) == 2 and (m.cur.name, 0) in nxt.inputs:
+            other = _other(nxt, (m.cur.name, 0))
             # by shape, not by size: [C], [1,1,1,C] or one element (a [C,1] constant scales along W)
             sv = _channel_const(_const(g, other), cout, 4)
-            if sv is not None and other != (cur.name, 0):
-                w = w * sv
-                bias = bias * sv
-                chain.append(nxt)
-                cur = nxt
-                nxt = c.only_consumer(cur.name)
+            if sv is not None and other != (m.cur.name, 0):
+                m.w = m.w * sv
+                m.bias = m.bias * sv
+                nxt = m.take(nxt)
         if nxt is not None and nxt.op in ("Add", "AddV2") and len(nxt.inputs) == 2:
-            other = nxt.inputs[1] if nxt.inputs[0] == (cur.name, 0) else nxt.inputs[0]
-            if other != (cur.name, 0) and _const(g, other) is None:
+            other = _other(nxt, (m.cur.name, 0))
+            if other != (m.cur.name, 0) and _const(g, other) is None:
                 residual = other
-                chain.append(nxt)
-                cur = nxt
-                nxt = c.only_consumer(cur.name)
+                nxt = m.take(nxt)
         # a GELU subgraph (erf or tanh form) closes the chain like a one-node activation: after the
         # residual add, which is the order of the kernels' epilogue
-        gelu = match_gelu(g, c, cur.name)
+        gelu = match_gelu(g, c, m.cur.name)
         if gelu is not None:
-            act, gnodes, out_node = gelu
-            chain += gnodes + [out_node]
-            cur = out_node
-        elif nxt is not None and nxt.op in _CLOSING_ACTS:
-            act = _CLOSING_ACTS[nxt.op]
-            chain.append(nxt)
-            cur = nxt
-        impl = FusedConv(w, bias, (strides[1], strides[2]), padding, pads, act, device, c.use_hip, cur.name)
-        inputs = [x_ref] + ([residual] if residual is not None else [])
-        _finalize(g, chain, "_FusedConv2D", inputs, {"_impl": impl})
+            m.act, gnodes, out_node = gelu
+            m.take(*gnodes, out_node)
+        else:
+            m.close(_CLOSING_ACTS)
+        impl = FusedConv(m.w, m.bias, m.strides, m.padding, m.pads, m.act, device, c.use_hip, m.cur.name)
+        inputs = [m.x_ref] + ([residual] if residual is not None else [])
+        _finalize(g, m.chain, "_FusedConv2D", inputs, {"_impl": impl})
         c.refresh()
 
 
 def fuse_depthwise(g, order, fed, fetch_refs, device, opts):
     """``[Pad ->] DepthwiseConv2dNative [-> BiasAdd] [-> FusedBatchNorm*] [-> Relu | Relu6 | _HardSwish | _Swish]``
-    -> ``_FusedDepthwiseConv2D``, under fuse_conv's guards (NHWC, dilation 1, a
-    constant 4-D filter, an inference BatchNorm whose only used output is y, no
-    fetch inside the chain, single consumers) and channel multiplier 1.  On the
-    GPU also C % 8 == 0 and a filter of at most 7 x 7 (kernels/dwconv.hip);
-    anything else stays on the reference op."""
+    -> ``_FusedDepthwiseConv2D``, under ``_match_conv_chain``'s guards (NHWC,
+    dilation 1, a constant 4-D filter, an inference BatchNorm whose only used
+    output is y, no fetch inside the chain, single consumers) and channel
+    multiplier 1.  On the GPU also C % 8 == 0 and a filter of at most 7 x 7
+    (kernels/dwconv.hip); anything else stays on the reference op."""
     c = _Ctx(g, order, fed, fetch_refs, device, opts)
+
+    def multiplier_1(w):
+        """The [kh, kw, ch, 1] filter as the op's [kh, kw, ch]."""
+        kh, kw, ch, mult = w.shape
+        return w.reshape(kh, kw, ch) if mult == 1 and (not c.use_hip or FusedDepthwiseConv.hip_ok(kh, kw, ch)) \
+            else None
     for name in order:
         n = g.nodes.get(name)
-        if n is None or n.op != "DepthwiseConv2dNative" or n.sattr("data_format", "NHWC") != "NHWC":
+        if n is None or n.op != "DepthwiseConv2dNative":
             continue
-        dil = n.attr("dilations", [1, 1, 1, 1]) or [1, 1, 1, 1]
-        if any(d != 1 for d in dil):
+        m = _match_conv_chain(g, c, n, multiplier_1)
+        if m is None:
             continue
-        w = _const(g, n.inputs[1])
-        if w is None or w.dim() != 4 or w.shape[3] != 1:
-            continue
-        kh, kw, ch, _mult = w.shape
-        if c.use_hip and not FusedDepthwiseConv.hip_ok(kh, kw, ch):
-            continue
-        x_ref = n.inputs[0]
-        padding = n.sattr("padding", "VALID")
-        pads = (0, 0, 0, 0)
-        chain: List[Node] = []
-        if padding == "EXPLICIT":
-            ep = n.attr("explicit_paddings", [])
-            if ep[0] or ep[1] or ep[6] or ep[7]:
-                continue
-            pads = (ep[2], ep[3], ep[4], ep[5])
-        prod = g.nodes.get(x_ref[0])
-        if (padding == "VALID" and prod is not None and prod.op == "Pad" and x_ref[1] == 0
-                and c.only_consumer(prod.name) is n):
-            pv = _const(g, prod.inputs[1])
-            if pv is not None:
-                p = [int(v) for v in pv.reshape(-1).tolist()]
-                if len(p) == 8 and p[0] == p[1] == p[6] == p[7] == 0 and min(p) >= 0:
-                    chain.append(prod)
-                    x_ref = prod.inputs[0]
-                    padding, pads = "EXPLICIT", (p[2], p[3], p[4], p[5])
-        strides = n.attr("strides", [1, 1, 1, 1])
-        w = w.float().reshape(kh, kw, ch)
-        bias = zeros(ch, w)
-        chain.append(n)
-        cur = n
-        act = "none"
-        nxt = c.only_consumer(cur.name)
-        if nxt is not None and nxt.op == "BiasAdd" and nxt.inputs[0] == (cur.name, 0):
-            b = _const(g, nxt.inputs[1])
-            if b is not None and tuple(b.shape) == (ch,):
-                bias = bias + b.float()
-                chain.append(nxt)
-                cur = nxt
-                nxt = c.only_consumer(cur.name)
-        if (nxt is not None and nxt.op in ("FusedBatchNorm", "FusedBatchNormV2", "FusedBatchNormV3")
-                and nxt.inputs[0] == (cur.name, 0)):
-            aff = _bn_affine(g, c, nxt)
-            if aff is not None and aff[0].numel() == ch:
-                w = w * aff[0]
-                bias = bias * aff[0] + aff[1]
-                chain.append(nxt)
-                cur = nxt
-                nxt = c.only_consumer(cur.name)
-        if nxt is not None and nxt.op in _CLOSING_ACTS:
-            act = _CLOSING_ACTS[nxt.op]
-            chain.append(nxt)
-            cur = nxt
-        impl = FusedDepthwiseConv(w, bias, (strides[1], strides[2]), padding, pads, act, device, c.use_hip, cur.name)
-        _finalize(g, chain, "_FusedDepthwiseConv2D", [x_ref], {"_impl": impl})
+        m.close(_CLOSING_ACTS)
+        impl =FusedDepthwiseConv(m.w, m.bias, m.strides, m.padding, m.pads, m.act, device, c.use_hip, m.cur.name)
+        _finalize(g, m.chain, "_FusedDepthwiseConv2D", [m.x_ref], {"_impl": impl})
         c.refresh()
 
 
@@ -2428,20 +2387,6 @@ def fuse_dual_conv(g, order, fed, fetch_refs, device, opts):
         n.attrs = {"_impl": impl}
         del g.nodes[r.name]
         c.refresh()
-
-
-def _bn_affine(g: Graph, c: _Ctx, bn: Node):
-    """(scale, shift) of an inference FusedBatchNorm with constant params whose
-    only used output is y, else None."""
-    if bn.op not in ("FusedBatchNorm", "FusedBatchNormV2", "FusedBatchNormV3") or bn.attr("is_training", False) \
-            or bn.sattr("data_format", "NHWC") != "NHWC" or bn.name in c.fetch_nodes:
-        return None
-    params = [_const(g, r) for r in bn.inputs[1:5]]
-    if any(p is None for p in params) or {i for _c, _p, i in c.cons.get(bn.name, [])} - {0}:
-        return None
-    gamma, beta, mean, var = (p.float().reshape(-1) for p in params)
-    scale = gamma * torch.rsqrt(var + float(bn.attr("epsilon", 1e-3)))
-    return scale, beta - mean * scale
 
 
 def fuse_post_activation(g, order, fed, fetch_refs, device, opts):

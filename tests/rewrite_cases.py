@@ -18,7 +18,8 @@ must make of it and what the fetches must be:
                    it), gpu=True: the HIP kernels' bounds (kernel_bounds.py)
     case.gpu       the device leg runs it (its reference is one fused op, or
                    fused ops whose stored intermediates the reference rounds)
-    case.raises    both programs must refuse the graph with ops.Unsupported
+    case.raises    both programs must refuse the graph with ops.Unsupported; "OpError": both must
+                   refuse the batch with ops.OpError and the same text (case.must still holds)
 
 Inputs and weights are bf16-valued, so one table serves both legs.  Constants
 that a pass could apply along the wrong axis are distinct along every axis and
@@ -45,10 +46,12 @@ import torch
 import torch.nn.functional as F
 
 import fused_op_refs as fr
+import gconv_bounds as gb
 import kernel_bounds as kb
 from kernel_bounds import BF, E, rnd
 
-FUSED_OPS = ("_FusedConv2D", "_FusedDepthwiseConv2D", "_FusedDualConv", "_FusedMatMul", "_GlobalAvgPool", "_MaxPool",
+FUSED_OPS = ("_FusedConv2D", "_FusedDepthwiseConv2D", "_FusedGroupedConv2D", "_FusedDualConv", "_FusedMatMul",
+             "_GlobalAvgPool", "_MaxPool",
              "_SoftmaxArgMax", "_LayerNorm", "_FusedQKV", "_Attention", "_EmbeddingLN", "_KeyMaskAdder",
              "_DenseSoftmax", "_ClassifierHead", "_StemPool", "_ChainConv", "_FusedMatMulLN")
 BN_EPS = 1e-3
@@ -113,9 +116,12 @@ class GB:
         return self.n("Conv2D", name, [x, w], strides=s, padding=padding, data_format=fmt, dilations=dl,
                       use_cudnn_on_gpu=True, explicit_paddings=list(ep))
 
-    def dw(self, x, w, stride=1, padding="SAME", name="dw", ep=()):
-        return self.n("DepthwiseConv2dNative", name, [x, self.c(w, name + "/w")], strides=[1, stride, stride, 1],
-                      padding=padding, data_format="NHWC", dilations=[1, 1, 1, 1], explicit_paddings=list(ep))
+    def dw(self, x, w, stride=1, padding="SAME", name="dw", fmt="NHWC", dil=1, ep=()):
+        w = w if isinstance(w, str) else self.c(w, name + "/w")
+        s = [1, stride, stride, 1] if fmt == "NHWC" else [1, 1, stride, stride]
+        dl = [1, dil, dil, 1] if fmt == "NHWC" else [1, 1, dil, dil]
+        return self.n("DepthwiseConv2dNative", name, [x, w], strides=s, padding=padding, data_format=fmt,
+                      dilations=dl, explicit_paddings=list(ep))
 
     def bias(self, x, b, name="bias"):
         return self.n("BiasAdd", name, [x, b if isinstance(b, str) else self.c(b, name + "/b")], data_format="NHWC")
@@ -160,10 +166,11 @@ class GB:
 class Aff:
     """A K-deep dot product and the elementwise steps after it, in fp64."""
 
-    def __init__(self, pre, dot, k, bf16_w=True):
+    def __init__(self, pre, dot, k, bf16_w=True, k_gpu=None):
         self.pre, self.mag, self.dot, self.k = pre, dot, dot, k
         self.steps, self.wfold = 0, False
         self.bf16_w = bf16_w          # the kernel's weights are bf16 (the depthwise filter stays fp32)
+        self.k_gpu = k_gpu or k       # the additions the kernel performs, where it pads K (gconv_bounds.k_slots)
 
     @classmethod
     def conv(cls, x, w_hwio, strides=(1, 1), padding="SAME", pads=(0, 0, 0, 0)):
@@ -182,13 +189,23 @@ class Aff:
         return cls(run(kb.d(x), wt), run(kb.d(x).abs(), wt.abs()), kh * kw, bf16_w=False)
 
     @classmethod
+    def gconv(cls, x, w_hwio, strides=(1, 1), padding="SAME", pads=(0, 0, 0, 0)):
+        """A grouped conv (the filter's in-depth divides the input's channels): kh kw Cg products per
+        output; kernels/gconv.hip adds its zero-filled K padding too (gconv_bounds.k_slots)."""
+        kh, kw, cg, _cout = w_hwio.shape
+        p = fr.tf_pads(x.shape[1], x.shape[2], kh, kw, strides[0], strides[1], padding, pads)
+        zero = torch.zeros(w_hwio.shape[3])
+        pre, mag = gb.gconv_parts(x, w_hwio, zero, tuple(strides), p)
+        return cls(pre, mag, kh * kw * cg, k_gpu=gb.k_slots(cg))
+
+    @classmethod
     def mm(cls, x, w_kn):
         pre, mag, k = fr.matmul_parts(x, w_kn)
         return cls(pre, mag, k)
 
     def _next(self, pre, mag, dot, wfold=None):
         a = Aff.__new__(Aff)
-        a.pre, a.mag, a.dot, a.k, a.bf16_w = pre, mag, dot, self.k, self.bf16_w
+        a.pre, a.mag, a.dot, a.k, a.bf16_w, a.k_gpu = pre, mag, dot, self.k, self.bf16_w, self.k_gpu
         a.steps, a.wfold = self.steps + 1, self.wfold if wfold is None else wfold
         return a
 
@@ -211,7 +228,7 @@ class Aff:
         rounding of folded weights."""
         out_f32 = (not gpu) or bool(out_f32)
         splits = GPU_SPLITS if gpu else 1
-        k = self.k + STEP * self.steps
+        k = (self.k_gpu if gpu else self.k) + STEP * self.steps
         if act == "relu6":        # Lipschitz 1, exact: the pre-activation's bound carries over
             ref, acc = self.pre.clamp(0.0, 6.0), kb.acc_bound(self.pre, self.mag, k, splits, "none")
         else:
@@ -295,45 +312,62 @@ def alone(b, fetches, hist):
     return make(b, fetches, must=hist, exact=True)
 
 
-# ================================================================== fuse_conv / fuse_depthwise
+# ================================================================== fuse_conv / fuse_depthwise / fuse_grouped_conv
 B, H, W, C = 2, 8, 8, 8            # Wo == H == Cout: a scale along the wrong axis type-checks
+CG = 4                             # the grouped filter's in-depth: two groups of C = 8 (kernels/gconv.hip takes 4)
 LINKS = ["Pad", "Conv2D", "BiasAdd", "FusedBatchNormV3", "Mul", "AddV2", "Relu"]
+# The three conv passes share one chain matcher (fused._match_conv_chain), so every near miss of the
+# shared head is run for each kind of conv: kind -> (pass, conv op, fused op)
+KINDS = {"dense": ("fuse_conv", "Conv2D", "_FusedConv2D"),
+         "depthwise": ("fuse_depthwise", "DepthwiseConv2dNative", "_FusedDepthwiseConv2D"),
+         "grouped": ("fuse_grouped_conv", "Conv2D", "_FusedGroupedConv2D")}
 
 
-def conv_data(c=C, k=3, seed=0, cin=None):
+def conv_data(c=C, k=3, seed=0, cin=None, kind="dense"):
     cin = cin or c
     x = bfv(rnd(B, H, W, cin, seed=seed + 1))
-    w = bfv(rnd(k, k, cin, c, scale=1.0 / math.sqrt(k * k * cin), seed=seed + 2))
+    depth = {"dense": cin, "depthwise": 1, "grouped": CG}[kind]      # products per output: k k depth
+    shape = (k, k, cin, 1) if kind == "depthwise" else (k, k, depth, c)
+    w = bfv(rnd(*shape, scale=1.0 / math.sqrt(k * k * depth), seed=seed + 2))
     bias = bfv(rnd(c, scale=0.3, seed=seed + 3))
     r = bfv(rnd(B, H, W, c, seed=seed + 4))
     return x, w, bias, r
 
 
-def _chain(tap, mode, act="Relu", depthwise=False):
+def kind_conv(b, kind, x, w, **kw):
+    """The conv node of `kind` (GB.conv / GB.dw arguments)."""
+    return b.dw(x, w, **kw) if kind == "depthwise" else b.conv(x, w, **kw)
+
+
+def kind_aff(kind, x, w, strides=(1, 1), padding="SAME", pads=(0, 0, 0, 0)):
+    if kind == "depthwise":
+        return Aff.dwconv(x, w.reshape(w.shape[:3]), strides, padding, pads)
+    return (Aff.gconv if kind == "grouped" else Aff.conv)(x, w, strides, padding, pads)
+
+
+def _chain(tap, mode, act="Relu", kind="dense"):
     """Pad -> Conv -> BiasAdd -> BN -> Mul -> Add -> Relu with link `tap`
-    fetched (mode "fetch") or read by a second op (a Tanh, mode "consumer")."""
-    x, w, bias, r = conv_data(seed=10)
-    if depthwise:
-        w = bfv(rnd(3, 3, C, 1, scale=1 / 3, seed=12))
+    fetched (mode "fetch") or read by a second op (a Tanh, mode "consumer").
+    The depthwise and the grouped chain have no scale and no residual: their
+    passes absorb neither."""
+    _pass, conv_op, fused = KINDS[kind]
+    dense = kind == "dense"
+    x, w, bias, r = conv_data(seed=10, kind=kind)
     params, sv = bn_params(C, 1), wave([C], 2)
     b = GB()
     xs, rs = b.ph("x", x), b.ph("r", r)
     t = [b.pad(xs, [0, 0, 1, 1, 1, 1, 0, 0])]
-    t.append(b.dw(t[-1], w, padding="VALID") if depthwise else b.conv(t[-1], w, padding="VALID"))
+    t.append(kind_conv(b, kind, t[-1], w, padding="VALID"))
     t.append(b.bias(t[-1], bias))
     t.append(b.bn(t[-1], params))
-    links = list(LINKS)
-    if depthwise:            # the depthwise chain has no scale and no residual
-        links = ["Pad", "DepthwiseConv2dNative", "BiasAdd", "FusedBatchNormV3", act]
-    else:
+    links = ["Pad", conv_op, "BiasAdd", "FusedBatchNormV3"] + (["Mul", "AddV2"] if dense else []) + [act]
+    if dense:
         t.append(b.bi("Mul", t[-1], b.c(sv, "scale"), "mul"))
         t.append(b.bi("AddV2", t[-1], rs, "add"))
-        links[-1] = act
     t.append(b.un(act, t[-1], "act"))
     fetches = [t[-1]]
     if tap is not None:
         fetches.append(t[tap] if mode == "fetch" else b.un("Tanh", t[tap], "tap"))
-    fused = "_FusedDepthwiseConv2D" if depthwise else "_FusedConv2D"
     must = {fused: 1}
     maybe = []
     if tap is not None:
@@ -342,18 +376,17 @@ def _chain(tap, mode, act="Relu", depthwise=False):
             must["Tanh"] = 1
         elif links[tap] == "FusedBatchNormV3":
             must["FusedBatchNormV3"] = 1      # a fetched BatchNorm keeps running as itself
-        if mode == "consumer" and not depthwise and links[tap] == "BiasAdd":
+        if mode == "consumer" and dense and links[tap] == "BiasAdd":
             # conv + bias with two readers, one of them a BatchNorm: fuse_post_activation
             # may write the BatchNorm as the conv's second output (CPU; 64-channel convs on the device)
             del must["FusedBatchNormV3"]
             maybe = ["FusedBatchNormV3"]
 
     def ref(gpu=False):
-        base = Aff.dwconv(x, w.reshape(3, 3, C), (1, 1), "EXPLICIT", (1, 1, 1, 1)) if depthwise else \
-            Aff.conv(x, w, (1, 1), "EXPLICIT", (1, 1, 1, 1))
+        base = kind_aff(kind, x, w, (1, 1), "EXPLICIT", (1, 1, 1, 1))
         a = [None, base, base.add(bias)]
         a.append(a[-1].bn(params))
-        if not depthwise:
+        if dense:
             a.append(a[-1].mul(sv))
             a.append(a[-1].add(r))
         out = [a[-1].out(act.lower(), gpu)]
@@ -381,7 +414,13 @@ def conv_positive_relu6():
 
 @case("fuse_depthwise", gpu=True)
 def depthwise_positive():
-    return _chain(None, "fetch", act="Relu6", depthwise=True)
+    return _chain(None, "fetch", act="Relu6", kind="depthwise")
+
+
+@case("fuse_grouped_conv", gpu=True)
+def grouped_positive():
+    """C = 8 in two groups of 4: kernels/gconv.hip's smallest shape on the device."""
+    return _chain(None, "fetch", kind="grouped")
 
 
 def conv_chain_link(tap, mode):
@@ -389,7 +428,12 @@ def conv_chain_link(tap, mode):
 
 
 def depthwise_chain_link(tap, mode):
-    return _chain(["Pad", "DepthwiseConv2dNative", "BiasAdd", "FusedBatchNormV3"].index(tap), mode, "Relu6", True)
+    return _chain(["Pad", "DepthwiseConv2dNative", "BiasAdd", "FusedBatchNormV3"].index(tap), mode, "Relu6",
+                  "depthwise")
+
+
+def grouped_chain_link(tap, mode):
+    return _chain(LINKS.index(tap), mode, kind="grouped")
 
 
 for _mode in ("fetch", "consumer"):
@@ -397,6 +441,8 @@ for _mode in ("fetch", "consumer"):
         case("fuse_conv", tap=_tap, mode=_mode)(conv_chain_link)
     for _tap in ("Pad", "DepthwiseConv2dNative", "BiasAdd", "FusedBatchNormV3"):
         case("fuse_depthwise", tap=_tap, mode=_mode)(depthwise_chain_link)
+    for _tap in LINKS[:4]:
+        case("fuse_grouped_conv", tap=_tap, mode=_mode)(grouped_chain_link)
 
 
 def _conv_then(build_tail, must_tail, ref_tail, k=1, gpu_ok=True, extra_feeds=()):
@@ -479,106 +525,135 @@ def conv_added_to_itself():
     return _conv_then(lambda b, y, f: b.bi("AddV2", y, y, "add"), {"AddV2": 1}, lambda a, gpu: a.mul(torch.tensor(2.0)).out("none", gpu))
 
 
+# ---- near misses of the shared head: the dense ones under their own names, then each for the other two kinds
 @case("fuse_conv", which="batch")
 @case("fuse_conv", which="channel")
-def conv_pad_outside_hw(which):
-    """A Pad of the batch or the channel axis is not the conv's padding."""
-    cin = C + 2 if which == "channel" else C
-    x, w, _b, _r = conv_data(k=3, seed=40, cin=cin)
-    x = x[..., :C]
+def conv_pad_outside_hw(which, kind="dense"):
+    """A Pad of the batch or the channel axis is not the conv's padding.  (The
+    channel Pad also hides the channel count from _channels_of: the grouped
+    conv behind it is fuse_conv's, and runs as Conv2D does.)"""
+    full = C if kind == "grouped" else C + 2          # the conv's input channels behind a channel Pad
+    x, w, _b, _r = conv_data(k=3, seed=40, cin=full if which == "channel" else C, kind=kind)
+    if which == "channel":
+        x = x[..., :full - 2]
     pads = [1, 0, 1, 1, 1, 1, 0, 0] if which == "batch" else [0, 0, 1, 1, 1, 1, 1, 1]
     b = GB()
-    y = b.conv(b.pad(b.ph("x", x), pads), w, padding="VALID")
+    y = kind_conv(b, kind, b.pad(b.ph("x", x), pads), w, padding="VALID")
     xp = F.pad(x, [pads[6], pads[7], pads[4], pads[5], pads[2], pads[3], pads[0], pads[1]])
-    return make(b, [y], {"Pad": 1, "_FusedConv2D": 1}, ref=lambda gpu=False: [Aff.conv(xp, w, (1, 1), "VALID").out("none", gpu)])
+    fused = "_FusedConv2D" if (kind, which) == ("grouped", "channel") else KINDS[kind][2]
+    return make(b, [y], {"Pad": 1, fused: 1},
+                ref=lambda gpu=False: [kind_aff(kind, xp, w, (1, 1), "VALID").out("none", gpu)])
 
 
 @case("fuse_conv")
-def conv_pad_before_same():
-    x, w, _b, _r = conv_data(k=3, seed=41)
+def conv_pad_before_same(kind="dense"):
+    x, w, _b, _r = conv_data(k=3, seed=41, kind=kind)
     b = GB()
-    y = b.conv(b.pad(b.ph("x", x), [0, 0, 1, 1, 1, 1, 0, 0]), w, padding="SAME")
+    y = kind_conv(b, kind, b.pad(b.ph("x", x), [0, 0, 1, 1, 1, 1, 0, 0]), w, padding="SAME")
     xp = F.pad(x, [0, 0, 1, 1, 1, 1])
-    return make(b, [y], {"Pad": 1, "_FusedConv2D": 1}, ref=lambda gpu=False: [Aff.conv(xp, w).out("none", gpu)])
+    return make(b, [y], {"Pad": 1, KINDS[kind][2]: 1}, ref=lambda gpu=False: [kind_aff(kind, xp, w).out("none", gpu)])
 
 
 @case("fuse_conv")
-def conv_explicit_paddings_with_a_batch_entry():
-    x, w, _b, _r = conv_data(k=3, seed=42)
+def conv_explicit_paddings_with_a_batch_entry(kind="dense"):
+    x, w, _b, _r = conv_data(k=3, seed=42, kind=kind)
     b = GB()
-    y = b.conv(b.ph("x", x), w, padding="EXPLICIT", ep=[1, 0, 1, 1, 1, 1, 0, 0])
-    return alone(b, [y], {"Conv2D": 1})
+    y = kind_conv(b, kind, b.ph("x", x), w, padding="EXPLICIT", ep=[1, 0, 1, 1, 1, 1, 0, 0])
+    return alone(b, [y], {KINDS[kind][1]: 1})
 
 
 @case("fuse_conv")
-def conv_explicit_paddings_with_a_channel_entry():
-    x, w, _b, _r = conv_data(k=3, seed=46)
+def conv_explicit_paddings_with_a_channel_entry(kind="dense"):
+    x, w, _b, _r = conv_data(k=3, seed=46, kind=kind)
     b = GB()
-    y = b.conv(b.ph("x", x), w, padding="EXPLICIT", ep=[0, 0, 1, 1, 1, 1, 0, 1])
-    return alone(b, [y], {"Conv2D": 1})
+    y = kind_conv(b, kind, b.ph("x", x), w, padding="EXPLICIT", ep=[0, 0, 1, 1, 1, 1, 0, 1])
+    return alone(b, [y], {KINDS[kind][1]: 1})
 
 
 @case("fuse_conv")
-def conv_nchw():
-    x, w, _b, _r = conv_data(k=3, seed=43)
+def conv_nchw(kind="dense"):
+    x, w, _b, _r = conv_data(k=3, seed=43, kind=kind)
     b = GB()
-    y = b.un("Relu", b.conv(b.ph("x", x), w, fmt="NCHW"))
-    return alone(b, [y], {"Conv2D": 1, "Relu": 1})
+    y = b.un("Relu", kind_conv(b, kind, b.ph("x", x), w, fmt="NCHW"))
+    return alone(b, [y], {KINDS[kind][1]: 1, "Relu": 1})
 
 
 @case("fuse_conv")
-def conv_dilation_2():
-    x, w, _b, _r = conv_data(k=3, seed=44)
+def conv_dilation_2(kind="dense"):
+    x, w, _b, _r = conv_data(k=3, seed=44, kind=kind)
     b = GB()
-    y = b.un("Relu", b.conv(b.ph("x", x), w, dil=2))
-    return alone(b, [y], {"Conv2D": 1, "Relu": 1})
+    y = b.un("Relu", kind_conv(b, kind, b.ph("x", x), w, dil=2))
+    return alone(b, [y], {KINDS[kind][1]: 1, "Relu": 1})
 
 
 @case("fuse_conv")
-def conv_filter_is_fed():
-    x, w, _b, _r = conv_data(k=3, seed=45)
-    b = GB()
-    xs = b.ph("x", x)
-    y = b.un("Relu", b.conv(xs, b.ph("w", w, dyn_batch=False)))
-    return alone(b, [y], {"Conv2D": 1, "Relu": 1})
-
-
-def _conv_bn():
-    x, w, _b, _r = conv_data(k=1, seed=50)
-    params = bn_params(C, 5)
+def conv_filter_is_fed(kind="dense"):
+    x, w, _b, _r = conv_data(k=3, seed=45, kind=kind)
     b = GB()
     xs = b.ph("x", x)
-    return b, xs, x, w, params
+    y = b.un("Relu", kind_conv(b, kind, xs, b.ph("w", w, dyn_batch=False)))
+    return alone(b, [y], {KINDS[kind][1]: 1, "Relu": 1})
+
+
+def _conv_bn(kind="dense", c_bn=C):
+    """x, a 1x1 conv of `kind` on it, and BatchNorm parameters of `c_bn` elements."""
+    x, w, _b, _r = conv_data(k=1, seed=50, kind=kind)
+    params = bn_params(c_bn, 5)
+    b = GB()
+    xs = b.ph("x", x)
+    return b, kind_conv(b, kind, xs, w), x, w, params
 
 
 @case("fuse_conv")
-def conv_bn_is_training():
-    b, xs, x, w, params = _conv_bn()
-    y = b.un("Relu", b.bn(b.conv(xs, w), params, training=True))
+def conv_bn_is_training(kind="dense"):
+    b, y, x, w, params = _conv_bn(kind)
+    y = b.un("Relu", b.bn(y, params, training=True))
     return make(b, [y], raises=True)
 
 
 @case("fuse_conv")
-def conv_bn_parameter_is_fed():
-    b, xs, x, w, params = _conv_bn()
+def conv_bn_parameter_is_fed(kind="dense"):
+    b, y, x, w, params = _conv_bn(kind)
     gamma = b.ph("gamma", bfv(params[0]), dyn_batch=False)
-    y = b.un("Relu", b.bn(b.conv(xs, w), (gamma,) + tuple(params[1:])))
+    y = b.un("Relu", b.bn(y, (gamma,) + tuple(params[1:])))
     p = (bfv(params[0]),) + tuple(params[1:])
-    return make(b, [y], {"_FusedConv2D": 1, "FusedBatchNormV3": 1, "Relu": 1},
-                ref=lambda gpu=False: [Aff.conv(x, w).bn(p).out("relu", gpu)])
+    return make(b, [y], {KINDS[kind][2]: 1, "FusedBatchNormV3": 1, "Relu": 1},
+                ref=lambda gpu=False: [kind_aff(kind, x, w).bn(p).out("relu", gpu)])
 
 
 @case("fuse_conv", out=1)
 @case("fuse_conv", out=2)
 @case("fuse_conv", out=3)
 @case("fuse_conv", out=4)
-def conv_bn_statistic_consumed(out):
-    b, xs, x, w, params = _conv_bn()
-    bn = b.bn(b.conv(xs, w), params)
+def conv_bn_statistic_consumed(out, kind="dense"):
+    b, y, x, w, params = _conv_bn(kind)
+    bn = b.bn(y, params)
     y = b.un("Relu", bn)
     stat = params[2] if out in (1, 3) else params[3]
-    return make(b, [y, f"{bn}:{out}"], {"_FusedConv2D": 1, "FusedBatchNormV3": 1, "Relu": 1},
-                ref=lambda gpu=False: [Aff.conv(x, w).bn(params).out("relu", gpu), exact(stat)])
+    return make(b, [y, f"{bn}:{out}"], {KINDS[kind][2]: 1, "FusedBatchNormV3": 1, "Relu": 1},
+                ref=lambda gpu=False: [kind_aff(kind, x, w).bn(params).out("relu", gpu), exact(stat)])
+
+
+for _kind in ("depthwise", "grouped"):
+    for _fn in (conv_pad_before_same, conv_explicit_paddings_with_a_batch_entry,
+                conv_explicit_paddings_with_a_channel_entry, conv_nchw, conv_dilation_2, conv_filter_is_fed,
+                conv_bn_is_training, conv_bn_parameter_is_fed):
+        case(KINDS[_kind][0], kind=_kind)(_fn)
+    for _which in ("batch", "channel"):
+        case(KINDS[_kind][0], which=_which, kind=_kind)(conv_pad_outside_hw)
+    for _out in (1, 2, 3, 4):
+        case(KINDS[_kind][0], out=_out, kind=_kind)(conv_bn_statistic_consumed)
+
+
+@case("fuse_conv")
+def conv_bn_has_another_element_count():
+    """A BatchNorm of C + 1 elements behind a conv with C outputs is no valid
+    graph: the BatchNorm is not folded (the conv fuses without it, as the
+    depthwise and the grouped pass always did), stays the interpreter's op, and
+    refuses the batch with the same error in both programs."""
+    b, y, _x, _w, params = _conv_bn(c_bn=C + 1)
+    y = b.un("Relu", b.bn(y, params))
+    return make(b, [y], {"_FusedConv2D": 1, "FusedBatchNormV3": 1, "Relu": 1}, raises="OpError")
 
 
 @case("fuse_conv", gpu=True)

@@ -282,3 +282,55 @@ def test_stem_pool_ideal_within_bound_and_mutants_rejected(even, pool_padding, p
         rejected(ideal((p[1], p[0], p[3], p[2]), pp), ref, bound, "conv pads on the other side")
     if pp[0] != pp[1] or pp[2] != pp[3]:
         rejected(ideal(p, (pp[1], pp[0], pp[3], pp[2])), ref, bound, "pool pads on the other side")
+
+
+# ================================================================== (c) the window geometry the conv and pool ops share
+def windows(k, s, padding, pads):
+    """One op of every class that is a window, k x k at stride s (C = 8, the grouped conv in two groups)."""
+    conv = (rnd(8, seed=1), (s, s), padding, pads, "none", CPU, False)
+    return [FU.FusedConv(rnd(k, k, 8, 8, seed=2), *conv, "dense"),
+            FU.FusedDepthwiseConv(rnd(k, k, 8, seed=3), *conv, "depthwise"),
+            FU.FusedGroupedConv(rnd(k, k, 4, 8, seed=4), *conv, "grouped", 8),
+            FU.MaxPool((k, k), (s, s), padding, False, pads)]
+
+
+@pytest.mark.parametrize("padding", ["SAME", "VALID", "EXPLICIT"])
+@pytest.mark.parametrize("s", [1, 2])
+@pytest.mark.parametrize("k", [1, 3, 5, 7])
+def test_window_geometry_is_tensorflows(k, s, padding):
+    """pads_for and out_hw of every window class against fused_op_refs, for odd
+    and even sizes 1..9 (h and w differ, w = 10 - h), and against the shape of
+    what the ops compute wherever the padded input holds a window."""
+    pads = (1, 2, 0, 1)                 # EXPLICIT: uneven on both axes
+    x9 = rnd(1, 9, 9, 8, seed=5)
+    for op in windows(k, s, padding, pads):
+        for h in range(1, 10):
+            w = 10 - h
+            p = fr.tf_pads(h, w, k, k, s, s, padding, pads)
+            assert op.pads_for(h, w) == p
+            want = fr.out_hw(h, w, k, k, s, s, p)
+            assert op.out_hw(h, w, p) == want, (type(op).__name__, h, w)
+            if min(want) >= 1:
+                y = op(None, None, [x9[:, :h, :w]])[0]
+                assert tuple(y.shape) == (1,) + want + (8,), (type(op).__name__, h, w, tuple(y.shape))
+
+
+def test_window_same_split_is_uneven_at_stride_2():
+    """An even size under an odd filter at stride 2: one row / column of padding, behind."""
+    for op in windows(3, 2, "SAME", (0, 0, 0, 0)):
+        assert op.pads_for(8, 6) == (0, 1, 0, 1) and op.out_hw(8, 6, (0, 1, 0, 1)) == (4, 3)
+        assert op.pads_for(9, 7) == (1, 1, 1, 1) and op.out_hw(9, 7, (1, 1, 1, 1)) == (5, 4)
+
+
+@pytest.mark.parametrize("k,s", [(7, 2), (3, 1), (5, 2)])
+def test_window_override_is_the_padded_rgba_filter(k, s):
+    """FusedConv's RGB(A) path computes with a khp x 8 filter over an image it
+    sizes itself: out_hw with that extent gives the plain conv's output size back."""
+    op = FU.FusedConv(rnd(k, k, 3, 16, seed=6), rnd(16, seed=7), (s, s), "SAME", (0, 0, 0, 0), "none", CPU, True, "c")
+    assert op.c4 and op.khp == k + 1
+    for h, w in ((9, 6), (8, 7), (4, 5)):
+        p = op.pads_for(h, w)
+        ho, wo = op.out_hw(h, w, p)
+        assert (ho, wo) == fr.out_hw(h, w, k, k, s, s, p)
+        hp, wp = (ho - 1) * s + op.khp, (wo - 1) * s + 8
+        assert op.out_hw(hp, wp, (0, 0, 0, 0), op.khp, 8) == (ho, wo) == fr.out_hw(hp, wp, op.khp, 8, s, s, (0,) * 4)

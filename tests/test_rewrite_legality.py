@@ -65,9 +65,14 @@ def test_case(entry):
     case = entry.build()
     plain, fused = compile_both(case.b.g, case.b.feeds, case.fetches)
     if case.raises:
+        texts = []
         for prog in (plain, fused):
-            with pytest.raises(O.Unsupported):
+            with pytest.raises(O.OpError if case.raises == "OpError" else O.Unsupported) as refusal:
                 prog.run(list(case.b.inputs))
+            texts.append(str(refusal.value))
+        if case.raises == "OpError":
+            check_histogram(case, fused.op_histogram())
+            assert texts[0] == texts[1], f"the fused program's error differs: {texts}"
         return
     a, b = plain.run(list(case.b.inputs)), fused.run(list(case.b.inputs))
     check_same_signature(a, b, case.fetches)
