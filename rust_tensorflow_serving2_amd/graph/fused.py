@@ -45,7 +45,8 @@ a single consumer and is not fetched):
   ``patch_tokens`` launch (kernels/misc.hip) from an fp32 ``[P + 1, C]`` table.
 * BERT: decomposed LayerNorm => ``_LayerNorm``; tanh/erf GELU subgraphs => act
   of the producing ``_FusedMatMul``; Q/K/V projections + attention core =>
-  ``_FusedQKV`` + ``_Attention`` (see ``bert_passes``).
+  ``_FusedQKV`` + ``_Attention`` (see ``bert_passes``); Swin's windowed attention as
+  ``_FusedQKV`` + ``_WindowAttention`` with the window layout folded into the op.
 
 On a CUDA/HIP device the fused ops launch the ``_hip`` kernels (bf16 operands,
 fp32 accumulate); on the CPU they run an fp32 torch reference of the *same*
@@ -1063,7 +1064,7 @@ def _impl_op(ctx, node, ins):
 for _op in ("_FusedConv2D", "_FusedDepthwiseConv2D", "_FusedDepthwiseLN", "_FusedGroupedConv2D", "_FusedDualConv", "_FusedMatMul", "_GlobalAvgPool", "_MaxPool",
             "_SqueezeExcite", "_SqueezeExciteSigmoid",
             "_SoftmaxArgMax", "_LayerNorm",
-            "_FusedQKV", "_Attention", "_EmbeddingLN", "_KeyMaskAdder", "_DenseSoftmax", "_PatchTokens"):
+            "_FusedQKV", "_Attention", "_WindowAttention", "_EmbeddingLN", "_KeyMaskAdder", "_DenseSoftmax", "_PatchTokens"):
     O.OPS[_op] = _impl_op
 
 

@@ -391,6 +391,24 @@ def _tile(ctx, n, ins):
     return [to_torch(ins[0]).repeat(host_ints(ins[1]))]
 
 
+@op("Roll")
+def _roll(ctx, n, ins):
+    """tf.roll: ``shift`` and ``axis`` are scalars or vectors of equal length;
+    axes may be negative, shifts negative or larger than the axis (taken modulo
+    its length), and shifts of a repeated axis add up."""
+    if isinstance(ins[0], np.ndarray) and ins[0].dtype == object:
+        raise Unsupported("Roll on strings")
+    x = to_torch(ins[0])
+    shifts, axes = host_ints(ins[1]), host_ints(ins[2])
+    if len(shifts) != len(axes):
+        raise OpError(f"{n.name}: {len(shifts)} shifts for {len(axes)} axes")
+    if any(a < -x.dim() or a >= x.dim() for a in axes):
+        raise OpError(f"{n.name}: axis out of range for rank {x.dim()}: {axes}")
+    if not axes or x.numel() == 0:
+        return [x]
+    return [torch.roll(x, shifts, axes)]
+
+
 @op("BroadcastTo")
 def _broadcast_to(ctx, n, ins):
     """tf.broadcast_to: numpy broadcasting of the input against ``shape``, which

@@ -14,12 +14,17 @@
       y = Reshape(Transpose(BatchMatMul(p, v), [0,2,1,3]), [-1, H*D])
         => _FusedQKV(x)  (one GEMM, concatenated weights)  ->  _Attention(qkv, mask_adder)
 
+* Swin's windowed attention (``fuse_window_attention``) and the roll / partition /
+  reverse layout around it (``fold_window_layout``)
+        => _FusedQKV(x)  ->  _WindowAttention(qkv; bias, mask, grid)
+
 Matching is strict: every interior node must be consumed only inside the
 pattern; anything else is left to the reference ops.
 """
 from __future__ import annotations
 
 import math
+import os
 from typing import Dict, List, Optional, Sequence, Set, Tuple
 
 import torch
@@ -151,10 +156,11 @@ class AttentionOp:
         adder = O.to_torch(ins[1]) if len(ins) > 1 else None
         S, H, D = self.s, self.h, self.d
         B = qkv.numel() // (S * 3 * H * D)
-        if adder is not None:
-            if adder.dim() != 4 or adder.shape[1] != 1 or adder.shape[-1] != S:
-                raise O.Unsupported("attention mask must be [B|1, 1, S|1, S]")
-        if self.use_hip and qkv.is_cuda and D == 64 and 1 <= S <= MAX_ATTENTION_SEQ:
+        # the kernel's adder is [B|1, 1, S|1, S]: one for all heads.  Any other adder that broadcasts
+        # against the [B, H, S, S] scores (a per-head [1, H, S, S] bias) takes the torch path below
+        kernel_adder = adder is None or (adder.dim() == 4 and adder.shape[1] == 1 and adder.shape[-1] == S and
+                                         adder.shape[0] in (1, B) and adder.shape[2] in (1, S))
+        if self.use_hip and qkv.is_cuda and D == 64 and 1 <= S <= MAX_ATTENTION_SEQ and kernel_adder:
             from ..ops import hip
             from .fused import _to_bf16
             q3 = _to_bf16(qkv).reshape(B, S, 3 * H * D).contiguous()
@@ -498,6 +504,446 @@ def fuse_attention(g, order, fed, fetch_refs, device, opts):
         c.refresh()
 
 
+# ------------------------------------------------------------------ windowed attention (Swin)
+WATTN_HEAD_DIM = 32           # kernels/launch.h kWattnHeadDim
+WATTN_MAX_SEQ = 64            # kernels/launch.h kWattnMaxSeq
+_BMM = ("BatchMatMul", "BatchMatMulV2", "BatchMatMulV3")
+
+
+def window_partition(x: torch.Tensor, ws: int) -> torch.Tensor:
+    """[B, Hf, Wf, C] -> [B * nW, ws * ws, C], windows row-major within an image."""
+    B, Hf, Wf, C = x.shape
+    x = x.reshape(B, Hf // ws, ws, Wf // ws, ws, C).permute(0, 1, 3, 2, 4, 5)
+    return x.reshape(-1, ws * ws, C)
+
+
+def window_reverse(x: torch.Tensor, ws: int, Hf: int, Wf: int) -> torch.Tensor:
+    """The inverse of window_partition: [B * nW, ws * ws, C] -> [B, Hf, Wf, C]."""
+    C = x.shape[-1]
+    x = x.reshape(-1, Hf // ws, Wf // ws, ws, ws, C).permute(0, 1, 3, 2, 4, 5)
+    return x.reshape(-1, Hf, Wf, C)
+
+
+class WindowAttentionOp:
+    """softmax(q k^T * scale + bias[h] (+ mask[w])) v within windows of ``s``
+    tokens over a packed QKV buffer [R, 3 * H * D].  ``grid`` None: window bw
+    owns rows [bw * s, (bw + 1) * s) and its mask window is bw % nW.  ``grid`` =
+    (Hf, Wf, ws, shift), set by fold_window_layout: the rows are in image order
+    and the op addresses the (shifted) windows itself, reading and writing in
+    place.  The kernel (kernels/wattn.hip) runs on the device for D = 32 and
+    s <= 64; the same mathematics with torch anywhere else, and always on the
+    CPU.  ``TFSERVE_WATTN=0`` forces the torch path (A/B only)."""
+
+    def __init__(self, heads: int, head_dim: int, seq: int, scale: float, bias: torch.Tensor,
+                 mask: Optional[torch.Tensor], device, use_hip: bool):
+        self.h, self.d, self.s, self.scale, self.use_hip = heads, head_dim, seq, float(scale), use_hip
+        self.grid = None
+        self.bias = to_device(bias.float().reshape(heads, seq, seq).contiguous(), device)
+        self.mask = None if mask is None else to_device(mask.float().reshape(-1, seq, seq).contiguous(), device)
+        self.nw = 0 if self.mask is None else int(self.mask.shape[0])
+
+    def kernel_ok(self, qkv: torch.Tensor) -> bool:
+        if not (self.use_hip and qkv.is_cuda and self.d == WATTN_HEAD_DIM and self.s <= WATTN_MAX_SEQ):
+            return False
+        if os.environ.get("TFSERVE_WATTN", "1") == "0":
+            return False
+        from ..ops import hip
+        R = qkv.numel() // (3 * self.h * self.d)
+        return bool(hip().window_attention_supported(R, self.s, self.h, self.d, self.nw,
+                                                     None if self.grid is None else list(self.grid)))
+
+    def _windows(self, qkv: torch.Tensor) -> torch.Tensor:
+        """The attention of rows in window order, [Bw * s, 3 * H * D] -> [Bw * s, H * D], in fp32."""
+        S, H, D = self.s, self.h, self.d
+        Bw = qkv.shape[0] // S
+        q, k, v = qkv.float().reshape(Bw, S, 3, H, D).permute(2, 0, 3, 1, 4)
+        sc = q @ k.transpose(-1, -2) * self.scale + self.bias.to(qkv.device)[None]
+        if self.mask is not None:
+            if Bw % self.nw:
+                raise O.OpError(f"{Bw} windows do not reshape to [-1, {self.nw}, {H}, {S}, {S}]")
+            sc = (sc.reshape(-1, self.nw, H, S, S) + self.mask.to(qkv.device)[None, :, None]).reshape(Bw, H, S, S)
+        return (torch.softmax(sc, -1) @ v).permute(0, 2, 1, 3).reshape(Bw * S, H * D)
+
+    def __call__(self, ctx, node, ins):
+        qkv = O.to_torch(ins[0])
+        S, H, D = self.s, self.h, self.d
+        W3 = 3 * H * D
+        if qkv.numel() % W3:
+            raise O.OpError(f"{node.name}: {list(qkv.shape)} is not [R, {W3}]")
+        R = qkv.numel() // W3
+        per = S if self.grid is None else self.grid[0] * self.grid[1]
+        if R % per:
+            raise O.OpError(f"{node.name}: {R} rows are not whole {'windows' if self.grid is None else 'maps'} of {per}")
+        qkv = qkv.reshape(R, W3)
+        if self.kernel_ok(qkv):
+            from ..ops import hip
+            from .fused import _to_bf16
+            return [hip().window_attention(_to_bf16(qkv).contiguous(), self.bias, self.mask, H, self.scale, None,
+                                           None if self.grid is None else list(self.grid))]
+        if self.grid is None:
+            y = self._windows(qkv)
+        else:
+            Hf, Wf, ws, sh = self.grid
+            x = qkv.reshape(-1, Hf, Wf, W3)
+            if sh:
+                x = torch.roll(x, (-sh, -sh), (1, 2))
+            y = window_reverse(self._windows(window_partition(x, ws).reshape(-1, W3)), ws, Hf, Wf)
+            if sh:
+                y = torch.roll(y, (sh, sh), (1, 2))
+            y = y.reshape(R, H * D)
+        return [y if not qkv.is_cuda else y.to(BF16)]
+
+
+def _ints(g, ref) -> Optional[List[int]]:
+    v = _const_t(g, ref)
+    if v is None or v.is_floating_point():
+        return None
+    return [int(x) for x in v.reshape(-1).tolist()]
+
+
+def _scale_of(g, n: Optional[Node]):
+    """n = Mul(x, c) (either order) or RealDiv(x, c) with a scalar c under fuse_attention's rules
+    -> (scale, x ref), else None."""
+    if n is None or len(n.inputs) != 2:
+        return None
+    if n.op == "Mul":
+        for k in (0, 1):
+            s = _scalar(g, n.inputs[k])
+            if s is not None:
+                return s, n.inputs[1 - k]
+    if n.op == "RealDiv":
+        dv = _const_t(g, n.inputs[1])
+        if dv is not None and dv.numel() == 1 and dv.dim() == 0 and dv.is_floating_point() and float(dv) != 0.0:
+            return 1.0 / float(dv), n.inputs[0]
+    return None
+
+
+def _packed_qkv(g, q_ref, k_ref, v_ref):
+    """q, k, v = Unpack(Transpose(Reshape(dense, [-1, S, 3, H, D]), [2, 0, 3, 1, 4])) -> (dense ref, S, H, D, nodes)."""
+    un = g.nodes.get(q_ref[0])
+    if un is None or un.op != "Unpack" or int(un.attr("axis", 0)) != 0:
+        return None
+    if (q_ref, k_ref, v_ref) != ((un.name, 0), (un.name, 1), (un.name, 2)):
+        return None
+    t = _node(g, un.inputs[0])
+    if t is None or t.op != "Transpose" or _ints(g, t.inputs[1]) != [2, 0, 3, 1, 4]:
+        return None
+    r = _node(g, t.inputs[0])
+    shp = _ints(g, r.inputs[1]) if r is not None and r.op == "Reshape" else None
+    if shp is None or len(shp) != 5 or shp[0] != -1 or shp[2] != 3 or min(shp[1:]) <= 0:
+        return None
+    return r.inputs[0], shp[1], shp[3], shp[4], [un, t, r]
+
+
+def fuse_window_attention(g, order, fed, fetch_refs, device, opts):
+    """Swin's attention core -> _FusedQKV -> _WindowAttention (see the module
+    docstring of kernels/wattn.hip for the arithmetic)::
+
+        scores = BatchMatMul(q', k, adj_y)                  q' = q or Mul(q, c)
+        scores = Mul(scores, c) | RealDiv(scores, c)        (at most one scale in all)
+        biased = AddV2(scores, bias)                        bias a constant [1, H, S, S] | [H, S, S]
+        masked = Reshape(AddV2(Reshape(biased, [-1, nW, H, S, S]), mask), [-1, H, S, S])     (optional)
+                                                            mask a constant [1, nW, 1, S, S] | [nW, 1, S, S]
+        y = Reshape(Transpose(BatchMatMul(Softmax(masked | biased), v), [0, 2, 1, 3]), [-1, H * D])
+
+    q, k, v from one packed dense (``_packed_qkv``: its columns are already in
+    the kernel's (3, H, D) order) or from three denses (``_heads_of``).  Only
+    D = 32: any other head width is fuse_attention's.  S is not limited here:
+    windows of more than 64 tokens (window 12) fuse too, and WindowAttentionOp then
+    computes them with torch on the device, in fp32 -- the kernel holds 64 keys."""
+    from .fused import FusedMatMul, _Ctx
+    c = _Ctx(g, order, fed, fetch_refs, device, opts)
+    for name in list(order):
+        out = g.nodes.get(name)
+        if out is None or out.op != "Reshape":
+            continue
+        t2 = _node(g, out.inputs[0])
+        if t2 is None or t2.op != "Transpose" or _ints(g, t2.inputs[1]) != [0, 2, 1, 3]:
+            continue
+        pv = _node(g, t2.inputs[0])
+        if pv is None or pv.op not in _BMM or pv.attr("adj_x", False) or pv.attr("adj_y", False):
+            continue
+        sm = _node(g, pv.inputs[0])
+        if sm is None or sm.op != "Softmax":
+            continue
+        interior = [t2, pv, sm]
+        cur = _node(g, sm.inputs[0])
+        mask = None
+        mshape = None
+        if cur is not None and cur.op == "Reshape":
+            # the shift mask: Reshape [-1, H, S, S] of AddV2(Reshape [-1, nW, H, S, S], mask)
+            back = _ints(g, cur.inputs[1])
+            add = _node(g, cur.inputs[0])
+            if back is None or len(back) != 4 or add is None or add.op not in ("Add", "AddV2") or len(add.inputs) != 2:
+                continue
+            for k in (0, 1):
+                r5, mv = _node(g, add.inputs[k]), _const_t(g, add.inputs[1 - k])
+                if r5 is not None and r5.op == "Reshape" and mv is not None:
+                    break
+            else:
+                continue
+            mshape = _ints(g, r5.inputs[1])
+            if mshape is None or len(mshape) != 5 or mshape[0] != -1 or back != [-1] + mshape[2:]:
+                continue
+            nW = mshape[1]
+            if tuple(mv.shape) not in ((1, nW, 1, mshape[3], mshape[4]), (nW, 1, mshape[3], mshape[4])) or nW < 1:
+                continue
+            mask = mv
+            interior += [cur, add, r5]
+            cur = _node(g, r5.inputs[0])
+        if cur is None or cur.op not in ("Add", "AddV2") or len(cur.inputs) != 2:
+            continue
+        for k in (0, 1):
+            bias, sc = _const_t(g, cur.inputs[1 - k]), _node(g, cur.inputs[k])
+            if bias is not None and sc is not None:
+                break
+        else:
+            continue
+        interior.append(cur)
+        scale = None
+        sv = _scale_of(g, sc) if sc.op in ("Mul", "RealDiv") else None
+        if sv is not None:
+            scale = sv[0]
+            interior.append(sc)
+            sc = _node(g, sv[1])
+        qk = sc
+        if qk is None or qk.op not in _BMM or qk.attr("adj_x", False) or not qk.attr("adj_y", False):
+            continue
+        interior.append(qk)
+        q_ref, k_ref, v_ref = qk.inputs[0], qk.inputs[1], pv.inputs[1]
+        qm = _node(g, q_ref)
+        if scale is None and qm is not None and qm.op == "Mul":
+            sv = _scale_of(g, qm)
+            if sv is None:
+                continue
+            scale, q_ref = sv
+            interior.append(qm)
+        packed = _packed_qkv(g, q_ref, k_ref, v_ref)
+        if packed is not None:
+            dense_ref, S, H, D, nodes = packed
+            interior += nodes
+            ds = _dense_src(g, c, dense_ref)
+            if ds is None or ds[1].shape[1] != 3 * H * D:
+                continue
+            x_ref, w, b, qkv_nodes = ds
+        else:
+            hq, hk, hv = _heads_of(g, c, q_ref), _heads_of(g, c, k_ref), _heads_of(g, c, v_ref)
+            if hq is None or hk is None or hv is None or hq[1:4] != hk[1:4] or hq[1:4] != hv[1:4]:
+                continue
+            S, H, D = hq[1:4]
+            interior += hq[4] + hk[4] + hv[4]
+            dq, dk, dv = _dense_src(g, c, hq[0]), _dense_src(g, c, hk[0]), _dense_src(g, c, hv[0])
+            if not (dq and dk and dv and dq[0] == dk[0] == dv[0]):
+                continue
+            if any(d[1].shape[1] != H * D for d in (dq, dk, dv)):
+                continue
+            x_ref = dq[0]
+            w = torch.cat([dq[1], dk[1], dv[1]], dim=1)
+            b = torch.cat([dq[2], dk[2], dv[2]])
+            qkv_nodes = dq[3] + dk[3] + dv[3]
+        if D != WATTN_HEAD_DIM:
+            continue
+        if tuple(bias.shape) not in ((1, H, S, S), (H, S, S)) or not bias.is_floating_point():
+            continue                  # by shape: a [1, 1, S, S] adder is fuse_attention's
+        if mask is not None and (mshape[2:] != [H, S, S] or not mask.is_floating_point()):
+            continue
+        if _ints(g, out.inputs[1]) != [-1, H * D]:
+            continue                  # (the op returns [R, H * D])
+        if not _interior_ok(c, interior + qkv_nodes, out):
+            continue
+        qkv_name = g.unique_name(out.name + "/fused_qkv")
+        g.add(Node(name=qkv_name, op="_FusedQKV", inputs=[x_ref],
+                   attrs={"_impl": FusedMatMul(w, b, "none", False, device, c.use_hip, qkv_name)}))
+        _remove(g, interior + qkv_nodes)
+        out.op = "_WindowAttention"
+        out.inputs = [(qkv_name, 0)]
+        out.ctrl = []
+        out.attrs = {"_impl": WindowAttentionOp(H, D, S, 1.0 if scale is None else scale, bias, mask, device,
+                                                c.use_hip)}
+        c.refresh()
+
+
+def _reshape_to(g, n: Optional[Node], want: Sequence[int]) -> bool:
+    return n is not None and n.op == "Reshape" and _ints(g, n.inputs[1]) == list(want)
+
+
+def _roll_of(g, n: Optional[Node]):
+    """n = Roll(x, [a, b], [1, 2]) with constant operands -> (a, b), else None."""
+    if n is None or n.op != "Roll" or len(n.inputs) != 3:
+        return None
+    shifts, axes = _ints(g, n.inputs[1]), _ints(g, n.inputs[2])
+    if shifts is None or axes != [1, 2] or len(shifts) != 2:
+        return None
+    return shifts[0], shifts[1]
+
+
+def _is_map(g, ref, Hf: int, Wf: int, C: int) -> bool:
+    """Whether ``ref`` is provably [.., Hf, Wf, C]: a Reshape to the constant [-1, Hf, Wf, C], or a
+    Placeholder declared with that static shape.  (The compiler infers no other shapes.)"""
+    n = _node(g, ref)
+    if _reshape_to(g, n, [-1, Hf, Wf, C]):
+        return True
+    if n is not None and n.op == "Placeholder":
+        shape = n.attrs.get("shape")
+        return isinstance(shape, tuple) and len(shape) == 4 and tuple(shape[1:]) == (Hf, Wf, C)
+    return False
+
+
+def _window_chain_up(g, qkv: Node, S: int, C: int, nw: int):
+    """[Reshape [-1, C]] <- Reshape [-1, S, C] <- Transpose <- Reshape 6-D <- [Roll] <- x, walked up from the
+    QKV GEMM -> (x ref, (Hf, Wf, ws, shift), (nwy, nwx), nodes), or None on a miss."""
+    nodes = []
+    up = _node(g, qkv.inputs[0])
+    if _reshape_to(g, up, [-1, C]):
+        nodes.append(up)
+        up = _node(g, up.inputs[0])
+    if not _reshape_to(g, up, [-1, S, C]):
+        return None
+    tp = _node(g, up.inputs[0])
+    if tp is None or tp.op != "Transpose" or _ints(g, tp.inputs[1]) != [0, 1, 3, 2, 4, 5]:
+        return None
+    r6 = _node(g, tp.inputs[0])
+    s6 = _ints(g, r6.inputs[1]) if r6 is not None and r6.op == "Reshape" else None
+    if s6 is None or len(s6) != 6 or s6[0] != -1 or min(s6[1:]) <= 0 or s6[2] != s6[4] or s6[5] != C:
+        return None
+    nwy, ws, nwx = s6[1], s6[2], s6[3]
+    Hf, Wf = nwy * ws, nwx * ws
+    if ws * ws != S or (nw and nw != nwy * nwx):
+        return None
+    nodes += [up, tp, r6]
+    x_ref, shift = r6.inputs[0], 0
+    roll = _node(g, x_ref)
+    if roll is not None and roll.op == "Roll":
+        by = _roll_of(g, roll)
+        if by is None or by[0] != by[1] or not -ws < by[0] < 0:
+            return None
+        # the Roll turns axes 1 and 2 of what it is given, the kernel an Hf x Wf map: they are the same
+        # only if the rolled tensor is [.., Hf, Wf, C].  (Without a Roll the flattening is layout-neutral.)
+        if not _is_map(g, roll.inputs[0], Hf, Wf, C):
+            return None
+        shift = -by[0]
+        nodes.append(roll)
+        x_ref = roll.inputs[0]
+    return x_ref, (Hf, Wf, ws, shift), (nwy, nwx), nodes
+
+
+def _window_chain_down(g, c, att: Node, C: int, grid, nwin):
+    """dense -> Reshape [-1, ws, ws, C] -> Reshape 6-D -> Transpose -> Reshape [-1, Hf, Wf, C] -> [Roll], walked
+    down from the attention -> (projection's last node, the chain's last node, nodes between), or None."""
+    Hf, Wf, ws, shift = grid
+    mm = c.only_consumer(att.name)
+    if mm is None or mm.op != "MatMul" or mm.inputs[0] != (att.name, 0) or mm.attr("transpose_a", False):
+        return None
+    wv = _const_t(g, mm.inputs[1])
+    if wv is None or wv.dim() != 2 or wv.shape[0 if mm.attr("transpose_b", False) else 1] != C:
+        return None
+    nodes, proj = [], mm
+    nxt = c.only_consumer(mm.name)
+    if nxt is not None and nxt.op in ("BiasAdd", "Add", "AddV2") and nxt.inputs[0] == (mm.name, 0):
+        bv = _const_t(g, nxt.inputs[1])
+        if bv is not None and bv.dim() <= 2 and _last_axis_const(bv) is not None:
+            nodes.append(mm)
+            proj = nxt
+            nxt = c.only_consumer(proj.name)
+    for want in ([-1, ws, ws, C], [-1, nwin[0], nwin[1], ws, ws, C]):
+        if not _reshape_to(g, nxt, want):
+            return None
+        nodes.append(nxt)
+        nxt = c.only_consumer(nxt.name)
+    if nxt is None or nxt.op != "Transpose" or _ints(g, nxt.inputs[1]) != [0, 1, 3, 2, 4, 5]:
+        return None
+    nodes.append(nxt)
+    last = c.only_consumer(nxt.name)
+    if not _reshape_to(g, last, [-1, Hf, Wf, C]):
+        return None
+    if shift:
+        nodes.append(last)
+        last = c.only_consumer(last.name)
+        if _roll_of(g, last) != (shift, shift):
+            return None
+    elif any(g.nodes[cn].op == "Roll" for cn, _p, _i in c.cons.get(last.name, [])):
+        return None                   # a roll on the way out only: not this chain
+    return proj, last, nodes
+
+
+def fold_window_layout(g, order, fed, fetch_refs, device, opts):
+    """Directly after fuse_window_attention: LayerNorm, the QKV GEMM and the
+    output projection are per token, so they commute with the window
+    permutation.  The chain::
+
+        x [B, Hf, Wf, C] -> [Roll(-s, -s; axes 1, 2)]
+          -> Reshape [-1, Hf/ws, ws, Wf/ws, ws, C] -> Transpose [0, 1, 3, 2, 4, 5] -> Reshape [-1, ws*ws, C]
+          -> [Reshape [-1, C]] -> _FusedQKV -> _WindowAttention -> dense
+          -> Reshape [-1, ws, ws, C]
+          -> Reshape [-1, Hf/ws, Wf/ws, ws, ws, C] -> Transpose [0, 1, 3, 2, 4, 5] -> Reshape [-1, Hf, Wf, C]
+          -> [Roll(+s, +s; axes 1, 2)]
+
+    becomes Reshape(x, [-1, C]) -> _FusedQKV -> _WindowAttention(grid = (Hf, Wf,
+    ws, s)) -> dense -> Reshape [-1, Hf, Wf, C]; a following Reshape [-1, C] of
+    that reads the dense directly, so the block's residual add meets the GEMM.
+    Every shape constant must agree, the rolls must be exact inverses with
+    0 < s < ws (or both absent), a rolled x must be provably [.., Hf, Wf, C]
+    (``_is_map``), and every interior node must have one reader and not be
+    fetched; anything else keeps the op between its layout nodes.  The fold
+    does not depend on the kernel: an op that takes its torch path (S > 64)
+    rolls and partitions inside itself.  ``TFSERVE_WATTN_FOLD=0`` turns the
+    pass off (A/B only)."""
+    from .fused import _Ctx
+    if os.environ.get("TFSERVE_WATTN_FOLD", "1") == "0":
+        return
+    c = _Ctx(g, order, fed, fetch_refs, device, opts)
+    for name in list(order):
+        att = g.nodes.get(name)
+        if att is None or att.op != "_WindowAttention" or att.attrs["_impl"].grid is not None:
+            continue
+        impl = att.attrs["_impl"]
+        C = impl.h * impl.d
+        qkv = _node(g, att.inputs[0])
+        if qkv is None or qkv.op != "_FusedQKV" or qkv.attrs["_impl"].k != C:
+            continue
+        up = _window_chain_up(g, qkv, impl.s, C, impl.nw)
+        if up is None:
+            continue
+        x_ref, grid, nwin, before = up
+        down = _window_chain_down(g, c, att, C, grid, nwin)
+        if down is None:
+            continue
+        proj, last, after = down
+        if not _interior_ok(c, [qkv, att, proj] + before + after, last):
+            continue
+        # ---- rewire
+        flat_name = g.unique_name(att.name + "/rows")
+        shape_name = g.unique_name(att.name + "/rows/shape")
+        g.add(Node(name=shape_name, op="Const", inputs=[], attrs={}, value=[torch.tensor([-1, C], dtype=torch.int32)]))
+        g.add(Node(name=flat_name, op="Reshape", inputs=[x_ref, (shape_name, 0)], attrs={}))
+        qkv.inputs = [(flat_name, 0)]
+        impl.grid = grid
+        map_shape = g.unique_name(att.name + "/map/shape")
+        g.add(Node(name=map_shape, op="Const", inputs=[], attrs={},
+                   value=[torch.tensor([-1, grid[0], grid[1], C], dtype=torch.int32)]))
+        mm = _node(g, proj.inputs[0]) if proj.op != "MatMul" else proj
+        _remove(g, [n for n in before + after if n not in (mm, proj)])
+        last.op = "Reshape"
+        last.inputs = [(proj.name, 0), (map_shape, 0)]
+        last.ctrl = []
+        last.attrs = {}
+        last.value = None
+        c.refresh()
+        # a Reshape [-1, C] of the map reads the projection's [R, C] rows as they are
+        if last.name in c.fetch_nodes:
+            continue
+        for cn, _p, _i in list(c.cons.get(last.name, [])):
+            rs = g.nodes[cn]
+            if _reshape_to(g, rs, [-1, C]) and rs.inputs[0] == (last.name, 0) and rs.name not in c.fetch_nodes:
+                for user in g.nodes.values():
+                    user.inputs = [(proj.name, 0) if ref == (rs.name, 0) else ref for ref in user.inputs]
+                del g.nodes[rs.name]
+        c.refresh()
+        if not c.cons.get(last.name):
+            del g.nodes[last.name]
+            c.refresh()
+
+
 # ------------------------------------------------------------------ embeddings
 class EmbeddingLNOp:
     """LN(sum of row gathers + position rows), the BERT embedding block
@@ -691,7 +1137,7 @@ def fuse_key_mask(g, order, fed, fetch_refs, device, opts):
 
 
 def bert_passes():
-    return [fuse_layernorm, fuse_embedding, fuse_attention, fuse_key_mask]
+    return [fuse_layernorm, fuse_embedding, fuse_window_attention, fold_window_layout, fuse_attention, fuse_key_mask]
 
 
 def late_passes():

@@ -1088,6 +1088,73 @@ Tensor attention(const Tensor& qkv, const c10::optional<Tensor>& mask_bias, int6
   return y;
 }
 
+// the (Hf, Wf, ws, shift) of a window_attention grid argument, zeros for None
+struct WattnGrid { int64_t Hf = 0, Wf = 0, ws = 0, shift = 0; };
+WattnGrid wattn_grid(const c10::optional<std::vector<int64_t>>& grid) {
+  WattnGrid g;
+  if (!grid.has_value()) return g;
+  TORCH_CHECK(grid->size() == 4, "window_attention: grid must be (Hf, Wf, ws, shift)");
+  g.Hf = (*grid)[0]; g.Wf = (*grid)[1]; g.ws = (*grid)[2]; g.shift = (*grid)[3];
+  TORCH_CHECK(g.Hf >= 1 && g.Wf >= 1 && g.ws >= 1, "window_attention: grid sizes must be positive");
+  return g;
+}
+
+// qkv: [R, 3*H*32] bf16; bias: [H, S, S] f32; mask: [nW, S, S] f32 or None; grid: None or (Hf, Wf, ws, shift)
+Tensor window_attention(const Tensor& qkv, const Tensor& bias, const c10::optional<Tensor>& mask, int64_t heads,
+                        double scale, const c10::optional<Tensor>& out,
+                        const c10::optional<std::vector<int64_t>>& grid) {
+  need(qkv, at::kBFloat16, "qkv");
+  need(bias, at::kFloat, "bias");
+  TORCH_CHECK(qkv.dim() == 2, "window_attention: qkv must be [R, 3*H*D]");
+  TORCH_CHECK(heads >= 1 && qkv.size(1) % (3 * heads) == 0, "window_attention: qkv width must be 3*heads*head_dim");
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(qkv.device());
+  const int64_t R = qkv.size(0), D = qkv.size(1) / (3 * heads);
+  TORCH_CHECK(D == tfsk::kWattnHeadDim, "window_attention kernel supports head_dim ", tfsk::kWattnHeadDim, ", got ", D);
+  TORCH_CHECK(bias.dim() == 3 && bias.size(1) == bias.size(2), "window_attention: bias must be [H, S, S]");
+  const int64_t S = bias.size(1);
+  TORCH_CHECK(S >= 1 && S <= tfsk::kWattnMaxSeq, "window_attention kernel supports 1 <= S <= ", tfsk::kWattnMaxSeq,
+              ", got S = ", S);
+  TORCH_CHECK(bias.size(0) == heads, "window_attention: bias has ", bias.size(0), " heads, expected ", heads);
+  int64_t nW = 0;
+  const float* mp = nullptr;
+  if (mask.has_value()) {
+    need(*mask, at::kFloat, "mask");
+    TORCH_CHECK(mask->dim() == 3 && mask->size(0) >= 1 && mask->size(1) == S && mask->size(2) == S,
+                "window_attention: mask must be [nW, ", S, ", ", S, "]");
+    TORCH_CHECK(aligned16(*mask), "window_attention: mask must be 16-byte aligned");
+    nW = mask->size(0);
+    mp = mask->data_ptr<float>();
+  }
+  const WattnGrid g = wattn_grid(grid);
+  if (g.ws > 0) {
+    TORCH_CHECK(g.Hf % g.ws == 0 && g.Wf % g.ws == 0, "window_attention: the ", g.Hf, " x ", g.Wf,
+                " map is not a multiple of the window ", g.ws);
+    TORCH_CHECK(g.ws * g.ws == S, "window_attention: window ", g.ws, " x ", g.ws, " does not have S = ", S, " tokens");
+    TORCH_CHECK(g.shift >= 0 && g.shift < g.ws, "window_attention: shift ", g.shift, " outside [0, ", g.ws, ")");
+    TORCH_CHECK(nW == 0 || nW == (g.Hf / g.ws) * (g.Wf / g.ws), "window_attention: mask has ", nW,
+                " windows, the map has ", (g.Hf / g.ws) * (g.Wf / g.ws));
+    TORCH_CHECK(R % (g.Hf * g.Wf) == 0, "window_attention: ", R, " rows are not whole ", g.Hf, " x ", g.Wf, " maps");
+  } else {
+    TORCH_CHECK(R % S == 0, "window_attention: ", R, " rows are not whole windows of ", S);
+  }
+  const int64_t lim = int64_t(1) << 31;
+  TORCH_CHECK(qkv.numel() * 2 < lim && bias.numel() * 4 < lim && nW * S * S * 4 < lim,
+              "window_attention: operands must be smaller than 2 GiB");
+  TORCH_CHECK(aligned16(qkv), "window_attention: qkv must be 16-byte aligned");
+  TORCH_CHECK(aligned16(bias), "window_attention: bias must be 16-byte aligned");
+  Tensor y = out.has_value() ? *out : torch::empty({R, heads * D}, qkv.options());
+  need(y, at::kBFloat16, "out");
+  TORCH_CHECK(y.numel() == R * heads * D, "window_attention: out has the wrong size");
+  TORCH_CHECK(aligned16(y), "window_attention: out must be 16-byte aligned");
+  TORCH_CHECK(tfsk::window_attention_supported(R, S, heads, D, nW, g.Hf, g.Wf, g.ws, g.shift),
+              "window_attention: unsupported launch");
+  check(tfsk::window_attention_launch(bf16p(qkv), bias.data_ptr<float>(), mp, bf16p_mut(y), R, int(S), int(heads),
+                                      int(nW), float(scale), int(g.Hf), int(g.Wf), int(g.ws), int(g.shift),
+                                      cur_stream(qkv)),
+        "window_attention");
+  return y;
+}
+
 // y[b, 0, :] = bf16(table[0, :]); y[b, 1 + p, :] = bf16(float(x[b, p, :]) + table[1 + p, :])
 // x: [B, P, C] bf16 (any leading shape with B * P * C elements per the arguments), table: [P + 1, C] f32
 Tensor patch_tokens(const Tensor& x, const Tensor& table, const c10::optional<Tensor>& out) {
@@ -1234,6 +1301,21 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     const int k = tfsk::attention_forms(int(std::min<int64_t>(std::max<int64_t>(S, 0), 1 << 30)), forms);
     return std::vector<int64_t>(forms, forms + k);
   }, "the forms attention takes at length S: [0], or [0, 1] where the ragged register kernel applies");
+  m.def("window_attention", &window_attention, py::arg("qkv"), py::arg("bias"), py::arg("mask"), py::arg("heads"),
+        py::arg("scale"), py::arg("out") = py::none(), py::arg("grid") = py::none(),
+        "windowed attention (Swin): S <= 64 tokens per window, 32-wide heads, per-head bias [H, S, S], optional "
+        "shift mask [nW, S, S]; grid = (Hf, Wf, ws, shift) addresses the windows in an image-order buffer");
+  m.def("window_attention_supported",
+        [](int64_t R, int64_t S, int64_t H, int64_t D, int64_t nW, const c10::optional<std::vector<int64_t>>& grid) {
+          if (grid.has_value() && grid->size() != 4) return false;
+          const bool on = grid.has_value();
+          const int64_t Hf = on ? (*grid)[0] : 0, Wf = on ? (*grid)[1] : 0, ws = on ? (*grid)[2] : 0,
+                        shift = on ? (*grid)[3] : 0;
+          if (on && (Hf < 1 || Wf < 1 || ws < 1)) return false;
+          return tfsk::window_attention_supported(R, S, H, D, nW, Hf, Wf, ws, shift);
+        },
+        py::arg("R"), py::arg("S"), py::arg("H"), py::arg("D"), py::arg("nW") = 0, py::arg("grid") = py::none(),
+        "whether window_attention takes R rows of H heads of width D in windows of S (nW mask windows, 0: no mask)");
   m.def("patch_tokens", &patch_tokens, "class token + patches + position embedding in one launch",
         py::arg("x"), py::arg("table"), py::arg("out") = py::none());
   m.def("patch_tokens_supported", [](int64_t b, int64_t p, int64_t c) { return tfsk::patch_tokens_supported(b, p, c); },

@@ -331,4 +331,20 @@ void attention_set_trace(long long* trace, int cap);
 // registers (default), -1 = env TFSERVE_ATTN_PLDS; returns the previous mode
 int attention_set_plds(int mode);
 
+// Windowed attention (Swin) over a packed QKV buffer [R][3*H*32] (bf16):
+// out[row, h, :] = softmax(Q K^T * scale + bias[h] (+ mask[w])) V within each
+// window of S <= 64 tokens; bias f32 [H][S][S], mask f32 [nW][S][S] or null.
+// ws == 0 (Hf = Wf = shift = 0): window bw owns rows [bw*S, (bw+1)*S), w = bw % nW.
+// ws > 0: rows in image order, R = B*Hf*Wf, S = ws*ws, token (i, j) of window
+// (b, wy, wx) is row b*Hf*Wf + ((wy*ws + i + shift) % Hf)*Wf + ((wx*ws + j + shift) % Wf),
+// w = wy*(Wf/ws) + wx, nW = (Hf/ws)*(Wf/ws).  hipErrorInvalidValue for anything
+// window_attention_supported (nW = 0: no mask) does not take.
+constexpr int kWattnHeadDim = 32;
+constexpr int kWattnMaxSeq = 64;
+bool window_attention_supported(int64_t R, int64_t S, int64_t H, int64_t D, int64_t nW, int64_t Hf, int64_t Wf,
+                                int64_t ws, int64_t shift);
+hipError_t window_attention_launch(const uint16_t* qkv, const float* bias, const float* mask, uint16_t* out, int64_t R,
+                                   int S, int H, int nW, float scale, int Hf, int Wf, int ws, int shift,
+                                   hipStream_t stream);
+
 }  // namespace tfsk

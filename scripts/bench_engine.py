@@ -20,7 +20,7 @@ def main():
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--baseline", action="store_true")
     ap.add_argument("--model", default="resnet50", choices=["resnet50", "resnet50-v2", "resnext50", "mobilenet-v1", "mobilenet-v2", "mobilenet-v3-large",
-                                                      "mobilenet-v3-small", "efficientnet-b0", "convnext-tiny", "vit-b16", "bert-base"])
+                                                      "mobilenet-v3-small", "efficientnet-b0", "convnext-tiny", "vit-b16", "swin-tiny", "bert-base"])
     ap.add_argument("--graph-tune", type=int, default=1, help="whole-graph tile re-tuning at capture (0 = off)")
     ap.add_argument("--windows", type=int, default=1,
                     help="timed windows of --iters replays each; above 1, graph_ms is their median and "
@@ -71,6 +71,13 @@ def main():
         s = Servable("vit", 1, path, opts)
         r = s.runner("serving_default", ["input"], ["classes", "probabilities"])
         flop_per_item = 2 * 17.6e9         # multiply-adds at 224 x 224, patch 16 (S = 197)
+    elif args.model == "swin-tiny":
+        from rust_tensorflow_serving2_amd.models import swin
+        if not args.model_dir:
+            swin.export(path)
+        s = Servable("swin", 1, path, opts)
+        r = s.runner("serving_default", ["input"], ["classes", "probabilities"])
+        flop_per_item = 2 * 4.5e9          # multiply-adds at 224 x 224, window 7
     elif args.model == "resnext50":
         if not args.model_dir:
             resnet.export(path, groups=32, width_per_group=4)        # ResNeXt-50 32x4d

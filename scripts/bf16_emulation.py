@@ -1,7 +1,8 @@
 #!/usr/bin/env python
 """What does bf16 storage alone cost a MobileNet (or, with --family resnext, a
 ResNeXt-50 32x4d; with --family efficientnet, an EfficientNet-B0; with --family
-convnext, a ConvNeXt-T; with --family vit, a ViT-S/16) end to end?  CPU only.
+convnext, a ConvNeXt-T; with --family vit, a ViT-S/16; with --family swin, a
+Swin-T) end to end?  CPU only.
 
 Exports a random-init model, runs the fp32 interpreter, and runs the fused
 CPU program a second time with the conv weights rounded to bf16 and the output of
@@ -25,12 +26,15 @@ program stores -- with everything else in fp32.  Prints, per input seed:
 `--vit-gains DENSE RESIDUAL QK` overrides models/vit.py's DENSE_GAIN, RESIDUAL_GAIN and QK_GAIN; with
 --family vit the GEMMs' bf16 outputs (everything but the fp32 head), the packed QKV, the attention
 output and the patch tokens are rounded as well, and --vit-config / --patch pick the model.
+`--swin-gains DENSE RESIDUAL QK` does the same for models/swin.py (--family swin, Swin-T, window 7; the
+same ops rounded, _WindowAttention in _Attention's place); `--swin-bias-std` overrides its BIAS_STD.
 
     python scripts/bf16_emulation.py --version v3_small --seeds 0 1 2 3 --trials 3
     python scripts/bf16_emulation.py --family resnext --seeds 3 4 --trials 1
     python scripts/bf16_emulation.py --family efficientnet --seeds 0 1 2 --trials 3
     python scripts/bf16_emulation.py --family convnext --seeds 0 1 2 --trials 3
     python scripts/bf16_emulation.py --family vit --image-size 224 --seeds 0 1 2 --trials 2
+    python scripts/bf16_emulation.py --family swin --image-size 224 --seeds 0 1 2 --trials 2
 """
 import argparse
 import os
@@ -47,7 +51,7 @@ from rust_tensorflow_serving2_amd.server.servable import Servable, ServableOptio
 OUTS = ["classes", "probabilities"]
 ROUNDED = ("_FusedConv2D", "_FusedGroupedConv2D", "_FusedDepthwiseConv2D", "_SqueezeExcite", "_SqueezeExciteSigmoid",
            "_FusedDepthwiseLN", "_LayerNorm")
-VIT_ROUNDED = ROUNDED + ("_FusedMatMul", "_FusedQKV", "_Attention", "_PatchTokens")
+VIT_ROUNDED = ROUNDED + ("_FusedMatMul", "_FusedQKV", "_Attention", "_WindowAttention", "_PatchTokens")
 
 
 def bf16(t):
@@ -86,11 +90,12 @@ def emulate(program, trial, ops=ROUNDED):
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
-    ap.add_argument("--family", default="mobilenet", choices=["mobilenet", "resnext", "efficientnet", "convnext", "vit"],
+    ap.add_argument("--family", default="mobilenet", choices=["mobilenet", "resnext", "efficientnet", "convnext", "vit", "swin"],
                     help="resnext: ResNeXt-50 32x4d at full width (tests/test_resnext_gpu.py's model); efficientnet: "
                          "EfficientNet-B0 at full width (tests/test_efficientnet_gpu.py's model); convnext: ConvNeXt-T "
                          "at full width and depth (tests/test_convnext_gpu.py's model); vit: ViT-S/16 "
-                         "(tests/test_vit_gpu.py's model, at --image-size 224); --version is MobileNet's")
+                         "(tests/test_vit_gpu.py's model, at --image-size 224); swin: Swin-T (tests/test_swin_gpu.py's "
+                         "model, at --image-size 224); --version is MobileNet's")
     ap.add_argument("--version", default="v3_small", choices=mobilenet.VERSIONS)
     ap.add_argument("--image-size", type=int, default=64)
     ap.add_argument("--model-seed", type=int, default=3)
@@ -102,6 +107,8 @@ def main():
     ap.add_argument("--layer-scale", type=float)
     ap.add_argument("--vit-gains", type=float, nargs=3, metavar=("DENSE", "RESIDUAL", "QK"))
     ap.add_argument("--vit-config", default="vit_small")
+    ap.add_argument("--swin-gains", type=float, nargs=3, metavar=("DENSE", "RESIDUAL", "QK"))
+    ap.add_argument("--swin-bias-std", type=float)
     ap.add_argument("--patch", type=int, default=16)
     a = ap.parse_args()
     if a.gated_gain is not None:
@@ -127,6 +134,13 @@ def main():
         a.version = f"{a.vit_config}/{a.patch}"
         gains = tuple(a.vit_gains) if a.vit_gains else (vit.DENSE_GAIN, vit.RESIDUAL_GAIN, vit.QK_GAIN)
         print(a.version, "dense / residual / qk gains", gains)
+    elif a.family == "swin":
+        from rust_tensorflow_serving2_amd.models import swin
+        a.version = "swin_tiny"
+        if a.swin_bias_std is not None:
+            swin.BIAS_STD = a.swin_bias_std
+        gains = tuple(a.swin_gains) if a.swin_gains else (swin.DENSE_GAIN, swin.RESIDUAL_GAIN, swin.QK_GAIN)
+        print(a.version, "dense / residual / qk gains", gains, "bias std", swin.BIAS_STD)
     elif a.family == "resnext":
         a.version = "resnext50"
     elif a.version.startswith("v3"):
@@ -139,6 +153,8 @@ def main():
         convnext.export(path, image_size=a.image_size, seed=a.model_seed, layer_scale_init=convnext.LAYER_SCALE_INIT)
     elif a.family == "vit":
         vit.export(path, config=a.vit_config, patch=a.patch, image_size=a.image_size, seed=a.model_seed, gains=gains)
+    elif a.family == "swin":
+        swin.export(path, config="swin_tiny", image_size=a.image_size, seed=a.model_seed, gains=gains)
     elif a.family == "resnext":
         from rust_tensorflow_serving2_amd.models import resnet
         resnet.export(path, groups=32, width_per_group=4, image_size=a.image_size, seed=a.model_seed)
@@ -147,7 +163,7 @@ def main():
     ref = Servable("m", 1, path, ServableOptions(device="cpu"))
     emu = Servable("m", 1, path, ServableOptions(device="cpu", fuse=True))
     trial = [0]
-    emulate(emu.runner("serving_default", ["input"], OUTS).program, trial, VIT_ROUNDED if a.family == "vit" else ROUNDED)
+    emulate(emu.runner("serving_default", ["input"], OUTS).program, trial, VIT_ROUNDED if a.family in ("vit", "swin") else ROUNDED)
     np.set_printoptions(precision=4, suppress=True)
     for s in a.seeds:
         x = np.random.default_rng(s).random((a.batch, a.image_size, a.image_size, 3), dtype=np.float32)

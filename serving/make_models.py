@@ -5,7 +5,7 @@ The reference downloads ``resnet_v2_fp32_savedmodel_NHWC`` and copies version
 Offline, we write random-init SavedModels of the same architectures in the
 same ``<root>/<name>/<version>/`` layout:
 
-    python serving/make_models.py --root serving/models [--models resnet,resnet_v2,resnext50,mobilenet,mobilenet_v2,mobilenet_v3_large,mobilenet_v3_small,efficientnet_b0,convnext_tiny,vit_b16,bert,half_plus_two]
+    python serving/make_models.py --root serving/models [--models resnet,resnet_v2,resnext50,mobilenet,mobilenet_v2,mobilenet_v3_large,mobilenet_v3_small,efficientnet_b0,convnext_tiny,vit_b16,swin_tiny,bert,half_plus_two]
 
 * ``resnet``        ResNet-50 v1.5 (NHWC, alias "input", outputs classes/probabilities)
 * ``resnet_v2``     ResNet-50 v2 pre-activation (the fetch.sh model's architecture)
@@ -16,6 +16,7 @@ same ``<root>/<name>/<version>/`` layout:
 * ``efficientnet_b0``  EfficientNet-B0 224 (Keras layout: swish, sigmoid-gated squeeze-excite, 5x5 depthwise convs)
 * ``convnext_tiny``  ConvNeXt-T 224 (Keras layout: 7x7 depthwise convs, LayerNorm, erf GELU, layer scale)
 * ``vit_b16``       ViT-B/16 224 (TF layout: patch conv, class token by Tile + ConcatV2, 12 pre-LN blocks, S = 197)
+* ``swin_tiny``     Swin-T 224 (TF layout: 4x4 patch conv, window 7, tf.roll shifted windows, packed QKV, patch merging)
 * ``bert``          BERT-base seq 128 (input_ids / input_mask / segment_ids)
 * ``half_plus_two`` TF Serving's canonical test model
 
@@ -61,6 +62,9 @@ def main(argv=None):
         elif m == "vit_b16":
             from rust_tensorflow_serving2_amd.models import vit
             vit.export(out, config="vit_base", patch=16, image_size=224, seed=args.seed)
+        elif m == "swin_tiny":
+            from rust_tensorflow_serving2_amd.models import swin
+            swin.export(out, config="swin_tiny", image_size=224, seed=args.seed)
         elif m == "bert":
             from rust_tensorflow_serving2_amd.models import bert
             bert.export(out, bert.BertConfig(), seed=args.seed)
