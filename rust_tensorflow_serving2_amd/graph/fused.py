@@ -234,6 +234,28 @@ def _grouped_conv_torch(x: torch.Tensor, w_hwio: torch.Tensor, bias: torch.Tenso
     return y.permute(0, 2, 3, 1) + bias.to(x.dtype)
 
 
+# The row-panel kernel (kernels/panel.hip) as further options of a wide 1x1
+# conv; TFSERVE_PANEL=0 (read once) removes them (A/B in one build).
+_PANEL = os.environ.get("TFSERVE_PANEL", "1") != "0"
+
+
+def panel_eligible(kh, kw, sh, sw, pads, cin, cout, act, post=None, c4=False) -> bool:
+    """A conv the row-panel kernel may take: 1x1, stride 1, unpadded, ``cin``
+    one of the kernel's depths, at least twice as wide as deep (a bottleneck's
+    expand conv: the wider the output, the more re-reads of A the panel saves),
+    act none / relu, no post-activation output.  (bf16 NHWC input: every conv
+    with ``cin % 8 == 0`` has it.)"""
+    return (kh == 1 and kw == 1 and sh == 1 and sw == 1 and not any(pads) and cin in (128, 256, 512) and
+            cout % 64 == 0 and cout >= 2 * cin and act in ("none", "relu") and post is None and not c4)
+
+
+def panel_key(x_shape, cout, has_res, act):
+    """The ``ops.tuned_choice`` key of a panel-eligible conv: option 0 = the
+    tile-config path, i = the i-th form of ``hip().conv1x1_panel_forms``.  A
+    key kind of its own, timed at load: not part of the committed table."""
+    return ("panel", tuple(x_shape), cout, bool(has_res), act)
+
+
 class FusedConv(_Window):
     """Conv2D(+folded BN/bias)(+residual)(+act).  Weights: HWIO fp32 (reference)
     and [Cout][Kpad] bf16 (kernel)."""
@@ -306,12 +328,38 @@ class FusedConv(_Window):
         outs = _with_post(self, _ref_act(y, self.act).contiguous())
         return [o.to(BF16) for o in outs] if self.use_hip else outs
 
-    def __call__(self, ctx, node, ins):
+    def panel_choice(self, ctx, node, ins) -> Optional[int]:
+        """The tuned choice between the tile-config path (0) and the row-panel
+        kernel's forms (1, 2, ...) for these inputs, made without a launch
+        unless it has to be timed; None when the conv is not offered to that
+        kernel.  ``ChainConv`` asks before its own choice, so the chain is timed
+        against the expand conv's best form as a separate launch."""
+        x = O.to_torch(ins[0])
+        res = O.to_torch(ins[1]) if len(ins) > 1 else None
+        if not (_PANEL and self.use_hip and x.is_cuda and x.dim() == 4 and x.shape[3] == self.cin):
+            return None
+        if not panel_eligible(self.kh, self.kw, self.sh, self.sw, self.pads_for(x.shape[1], x.shape[2]), self.cin,
+                              self.cout, self.act, self.post, self.c4):
+            return None
+        if res is not None and tuple(res.shape) != tuple(x.shape[:3]) + (self.cout,):
+            return None                 # (a broadcast residual: the tile path expands it)
+        from ..ops import hip, tuned_choice
+        forms = hip().conv1x1_panel_forms(x.shape[0] * x.shape[1] * x.shape[2], self.cout, self.cin)
+        if not forms:
+            return None
+        # option 0 is today's launch, and the pick during capture or without autotuning
+        opts = {i: (lambda i=i: self(ctx, node, ins, panel_pick=i)) for i in range(len(forms) + 1)}
+        pick = tuned_choice(panel_key(x.shape, self.cout, res is not None, self.act), opts, default=0)
+        return pick if pick in opts else 0
+
+    def __call__(self, ctx, node, ins, panel_pick=None):
         x = O.to_torch(ins[0])
         res = O.to_torch(ins[1]) if len(ins) > 1 else None
         pt, pb, pl, pr = self.pads_for(x.shape[1], x.shape[2])
         if not self.use_hip or x.shape[3] != self.cin:
             return self._torch(x, res, (pt, pb, pl, pr))
+        if panel_pick is None:
+            panel_pick = self.panel_choice(ctx, node, ins)
         from ..ops import ACT, hip, tuned_config
         if self.c4:
             # fp32 RGB request -> zero-bordered bf16 RGBA sized for the padded
@@ -356,6 +404,11 @@ class FusedConv(_Window):
         run = lambda c, s: H.conv2d(*args, cfg=c, out=out, splits=s, **kw_post)  # noqa
         # (ReLU6 and hard-swish are igemm epilogues only: those launches tune over the igemm configs)
         flags = {"relu6": True} if self.act in IGEMM_ONLY_ACTS else {}
+        if panel_pick:
+            # a wide expand conv on the row-panel kernel (kernels/panel.hip): form panel_pick of its forms
+            bm, ns = H.conv1x1_panel_forms(M, self.cout, self.cin)[panel_pick - 1]
+            H.conv1x1_panel(x, self.w, self.b, res, ACT[self.act], bm, ns, out=out)
+            return outs
         cfg, splits = tuned_config(key, M, self.cout, run, K, dma, aligned, halo=halo,
                                    cgemm_only=self.post is not None, stem=self.c4, **flags)
         run(cfg, splits)
@@ -1283,8 +1336,11 @@ class ChainConv:
         x = O.to_torch(ins[0])
         a, b = self.a, self.b
 
+        # the expand conv's own tuned choice (tile path or a row-panel form) is made first
+        pp = a.panel_choice(ctx, node, ins) if isinstance(a, FusedConv) else None
+
         def split():
-            y1 = a(ctx, node, ins)[0]
+            y1 = (a(ctx, node, ins) if pp is None else a(ctx, node, ins, panel_pick=pp))[0]
             return [y1, b(ctx, node, [y1])[0]]
         if self.dual:
             return self._call_dual(x, O.to_torch(ins[1]), split)

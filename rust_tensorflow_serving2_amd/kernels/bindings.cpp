@@ -788,6 +788,42 @@ std::vector<Tensor> conv_chain(const Tensor& x, const Tensor& w1, const Tensor& 
   return {y1, y2};
 }
 
+// A wide 1x1 conv (+ shortcut, act) on the row-panel kernel (panel.hip): a
+// workgroup owns bm rows x cout / nsplit columns and reads its rows of x once.
+Tensor conv1x1_panel(const Tensor& x, const Tensor& w, const Tensor& bias, const c10::optional<Tensor>& residual,
+                     int64_t act, int64_t bm, int64_t nsplit, const c10::optional<Tensor>& out) {
+  need(x, at::kBFloat16, "x");
+  need(w, at::kBFloat16, "w");
+  need(bias, at::kFloat, "bias");
+  TORCH_CHECK(x.dim() == 4, "conv1x1_panel: x must be NHWC");
+  const int64_t M64 = x.size(0) * x.size(1) * x.size(2);
+  const int K = x.size(3), N = w.size(0);
+  TORCH_CHECK(w.dim() == 2 && w.size(1) >= K && w.size(1) % 8 == 0, "conv1x1_panel: w [N][>= K, a multiple of 8]");
+  TORCH_CHECK(M64 < (int64_t(1) << 31) && tfsk::conv1x1_panel_supported(int(M64), N, K, int(bm), int(nsplit)),
+              "conv1x1_panel: unsupported shape M=", M64, " N=", N, " K=", K, " bm=", bm, " nsplit=", nsplit);
+  TORCH_CHECK(act == tfsk::kActNone || act == tfsk::kActRelu, "conv1x1_panel: act must be none or relu");
+  TORCH_CHECK(bias.numel() == N, "conv1x1_panel: bias size");
+  TORCH_CHECK(w.device() == x.device() && bias.device() == x.device(), "conv1x1_panel: tensors on different devices");
+  const uint16_t* rp = nullptr;
+  if (residual.has_value()) {
+    need(*residual, at::kBFloat16, "residual");
+    TORCH_CHECK(residual->dim() == 4 && residual->size(0) == x.size(0) && residual->size(1) == x.size(1) &&
+                    residual->size(2) == x.size(2) && residual->size(3) == N && residual->device() == x.device(),
+                "conv1x1_panel: residual [n][h][w][N]");
+    rp = bf16p(*residual);
+  }
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
+  Tensor y = out.has_value() ? *out : torch::empty({x.size(0), x.size(1), x.size(2), N}, x.options());
+  need(y, at::kBFloat16, "out");
+  TORCH_CHECK(y.numel() == M64 * N && y.device() == x.device(), "conv1x1_panel: out [n][h][w][N]");
+  TORCH_CHECK(aligned16(x) && aligned16(w) && aligned16(bias) && aligned16(y) && (!rp || aligned16(*residual)),
+              "conv1x1_panel: operands must be 16-byte aligned");
+  check(tfsk::conv1x1_panel_launch(bf16p(x), bf16p(w), int(w.size(1)), bias.data_ptr<float>(), rp, bf16p_mut(y),
+                                   int(M64), N, K, int(bm), int(nsplit), int(act), cur_stream(x)),
+        "conv1x1_panel");
+  return y;
+}
+
 Tensor global_avgpool(const Tensor& x, const c10::optional<Tensor>& out) {
   need(x, at::kBFloat16, "x");
   TORCH_CHECK(x.dim() == 4 && x.size(3) % 8 == 0, "global_avgpool: NHWC with C % 8 == 0");
@@ -1194,6 +1230,25 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv_chain_supported", [](int64_t k1, int64_t n1, int64_t n2, bool dual) {
     return tfsk::conv_chain_supported(int(k1), int(n1), int(n2), dual);
   }, py::arg("k1"), py::arg("n1"), py::arg("n2"), py::arg("dual") = false);
+  m.def("conv1x1_panel", &conv1x1_panel, "wide 1x1 conv (+residual, act) on the row-panel kernel: A read once",
+        py::arg("x"), py::arg("w"), py::arg("bias"), py::arg("residual"), py::arg("act"), py::arg("bm"),
+        py::arg("nsplit"), py::arg("out") = py::none());
+  m.def("conv1x1_panel_supported", [](int64_t m, int64_t n, int64_t k, int64_t bm, int64_t nsplit, int64_t act,
+                                      const c10::optional<int64_t>& res_stride) {
+    // act / res_stride: what the launch would be given (a residual's row stride must be n)
+    return m < (int64_t(1) << 31) && n < (int64_t(1) << 31) &&
+           tfsk::conv1x1_panel_supported(int(m), int(n), int(k), int(bm), int(nsplit)) &&
+           (act == tfsk::kActNone || act == tfsk::kActRelu) && (!res_stride.has_value() || *res_stride == n);
+  }, py::arg("m"), py::arg("n"), py::arg("k"), py::arg("bm"), py::arg("nsplit"), py::arg("act") = 0,
+        py::arg("res_stride") = py::none());
+  m.def("conv1x1_panel_forms", [](int64_t m, int64_t n, int64_t k) {
+    int bm[tfsk::kPanelMaxForms], ns[tfsk::kPanelMaxForms];
+    std::vector<std::pair<int64_t, int64_t>> forms;
+    if (m >= (int64_t(1) << 31) || n >= (int64_t(1) << 31)) return forms;
+    const int c = tfsk::conv1x1_panel_forms(int(m), int(n), int(k), bm, ns);
+    for (int i = 0; i < c; ++i) forms.emplace_back(bm[i], ns[i]);
+    return forms;
+  }, "the (bm, nsplit) forms of conv1x1_panel worth timing for an M x N x K conv (none: unsupported)");
   m.def("conv2d_dual", &conv2d_dual, "act(conv1x1(h) + conv1x1_stride(x) + bias) as one K-concatenated GEMM",
         py::arg("h"), py::arg("x"), py::arg("w"), py::arg("bias"), py::arg("sh"), py::arg("sw"), py::arg("act") = 0,
         py::arg("cfg") = 36, py::arg("out") = py::none(), py::arg("splits") = 1,

@@ -157,6 +157,20 @@ hipError_t conv_chain_launch(const uint16_t* x, const uint16_t* w1, int ldw1, co
                              uint16_t* y1, const uint16_t* w2, int ldw2, const float* b2, uint16_t* y2, int M, int K1,
                              int N1, int N2, int act1, int act2, hipStream_t s, const uint16_t* x2 = nullptr,
                              int K1a = 0);
+// Row-panel 1x1 conv (panel.hip): out = act(a w^T + bias (+ res)), a [M][K],
+// w [N][ldw >= K], res / out [M][N], all bf16 and dense; act none or relu.  A
+// workgroup owns bm rows x N / nsplit columns and reads its A rows once.
+// K in {128, 256, 512}, N and N / nsplit multiples of 64, bm in {64, 128}
+// (128 only with K <= 256), nsplit in {1, 2, 4, 8}, M * N * 2 < 2^31; anything
+// else is hipErrorInvalidValue and launches nothing.  conv1x1_panel_forms
+// writes the (bm, nsplit) pairs worth timing for a shape (at most
+// kPanelMaxForms; those with >= 128 workgroups unless none has) and returns
+// their count.
+constexpr int kPanelMaxForms = 6;
+bool conv1x1_panel_supported(int M, int N, int K, int bm, int nsplit);
+int conv1x1_panel_forms(int M, int N, int K, int* bm, int* nsplit);
+hipError_t conv1x1_panel_launch(const uint16_t* a, const uint16_t* w, int ldw, const float* bias, const uint16_t* res,
+                                uint16_t* out, int M, int N, int K, int bm, int nsplit, int act, hipStream_t s);
 // NHWC bf16 max-pool (TF SAME/VALID padding given explicitly).  With `scale`
 // (and `shift`): y = act(max * scale[c] + shift[c]) — a folded inference
 // BatchNorm (+ ReLU when act == 1) applied after the pooling.
