@@ -43,6 +43,9 @@ a single consumer and is not fetched):
 * ViT: ``AddV2(ConcatV2([Tile|BroadcastTo(cls, [batch, ..]), Reshape(x, [-1, P, C])], 1), pos)``
   => ``_PatchTokens(x, batch)``: class token, patches and position embedding in one
   ``patch_tokens`` launch (kernels/misc.hip) from an fp32 ``[P + 1, C]`` table.
+* DLRM (``graph/patterns.py``): ``Pack([x0?, Sum(GatherV2(table_f, ids_f, 0), 1) ..], 1)`` =>
+  ``_EmbeddingBag`` (kernels/embag.hip); ``[Pad(] ConcatV2([dense, GatherV2(Reshape(BatchMatMul(Z, Z,
+  adj_y), [-1, F F]), tril idx, 1)], 1) [)]`` => ``_DotInteraction`` (kernels/interact.hip).
 * BERT: decomposed LayerNorm => ``_LayerNorm``; tanh/erf GELU subgraphs => act
   of the producing ``_FusedMatMul``; Q/K/V projections + attention core =>
   ``_FusedQKV`` + ``_Attention`` (see ``bert_passes``); Swin's windowed attention as
@@ -1117,7 +1120,8 @@ def _impl_op(ctx, node, ins):
 for _op in ("_FusedConv2D", "_FusedDepthwiseConv2D", "_FusedDepthwiseLN", "_FusedGroupedConv2D", "_FusedDualConv", "_FusedMatMul", "_GlobalAvgPool", "_MaxPool",
             "_SqueezeExcite", "_SqueezeExciteSigmoid",
             "_SoftmaxArgMax", "_LayerNorm",
-            "_FusedQKV", "_Attention", "_WindowAttention", "_EmbeddingLN", "_KeyMaskAdder", "_DenseSoftmax", "_PatchTokens"):
+            "_FusedQKV", "_Attention", "_WindowAttention", "_EmbeddingLN", "_KeyMaskAdder", "_DenseSoftmax", "_PatchTokens",
+            "_EmbeddingBag", "_DotInteraction"):
     O.OPS[_op] = _impl_op
 
 
@@ -2554,9 +2558,9 @@ def fuse_conv_chain(g, order, fed, fetch_refs, device, opts):
 
 
 def default_passes(options=None):
-    from .patterns import bert_passes, late_passes
+    from .patterns import bert_passes, dlrm_passes, late_passes
     return [fuse_pools, fuse_softmax_argmax, fuse_hard_activations, fuse_swish, fuse_squeeze_excite,
-            fuse_squeeze_excite_sigmoid] + bert_passes() + \
+            fuse_squeeze_excite_sigmoid] + bert_passes() + dlrm_passes() + \
         [fuse_grouped_conv, fuse_conv, fuse_patch_tokens, fuse_depthwise, fuse_depthwise_layernorm,
          fuse_dual_conv, fuse_post_activation, fuse_stem_pool, fuse_matmul,
          fuse_classifier_head, fuse_dense_softmax, fuse_conv_chain] + late_passes() + \

@@ -1136,6 +1136,328 @@ def fuse_key_mask(g, order, fed, fetch_refs, device, opts):
         c.refresh()
 
 
+# ------------------------------------------------------------------ DLRM: embedding bags, dot interaction
+class EmbeddingBagOp:
+    """``Pack([x_0?, e_0 .. e_{F-1}], axis=1)`` (or ``Reshape(ConcatV2(.., axis=1), [-1, F0 + F, D])``)
+    with ``e_f = Sum(GatherV2(table_f, ids_f, axis 0), axis=1)``: on the GPU one ``embedding_bag``
+    launch (kernels/embag.hip) from one bf16 blob of all tables, rounded once here from the fp32
+    variables as EmbeddingLNOp holds its tables.  ``split``: the id tensors were the outputs of one
+    ``SplitV(sparse, sizes, axis=1)``, and the op reads ``sparse [B, T]`` itself; otherwise it takes
+    the F id tensors ``[B, L_f]`` and concatenates them on the device.  The CPU, and any input the
+    kernel does not take, get the replaced nodes' own semantics from torch; on the CPU an id outside
+    its table raises as the interpreter's GatherV2 does, on the device it adds a zero row (a select,
+    never a product: the clamped row may hold Inf)."""
+
+    def __init__(self, tables, split, lead: bool, concat: bool, device, use_hip: bool, name: str):
+        self.vocab = [int(t.shape[0]) for t in tables]
+        self.d = int(tables[0].shape[1])
+        self.split = None if split is None else [int(s) for s in split]
+        self.lead, self.concat = bool(lead), bool(concat)
+        self.use_hip = use_hip
+        self.name = name
+        self.base = [sum(self.vocab[:f]) for f in range(len(tables))]
+        blob = torch.cat([t.reshape(v, self.d) for t, v in zip(tables, self.vocab)], dim=0)
+        self.blob = to_device(blob, device, BF16 if use_hip else torch.float32)
+        self._feat = {}                 # hotness tuple -> (flat host list, device [F, 4] int64)
+        if use_hip and self.split is not None and self.blob.is_cuda:
+            self.features(self.split, self.blob.device)
+
+    def features(self, hot, device):
+        """(row base, V, first slot, hotness) per feature: the flat host list the binding checks
+        and the device array the kernel reads (cached per hotness tuple: built before any capture
+        when the ids come from a SplitV, whose sizes are constants)."""
+        key = (tuple(hot), str(device))
+        if key not in self._feat:
+            flat, first = [], 0
+            for base, v, l in zip(self.base, self.vocab, hot):
+                flat += [base, v, first, int(l)]
+                first += int(l)
+            self._feat[key] = (flat, torch.tensor(flat, dtype=torch.int64).view(-1, 4).to(device))
+        return self._feat[key]
+
+    def _rows(self, node, f: int, idx: torch.Tensor) -> torch.Tensor:
+        """Sum(GatherV2(table_f, idx, axis 0), axis=1) in fp32."""
+        base, v = self.base[f], self.vocab[f]
+        flat = idx.reshape(-1).to(self.blob.device).long()
+        if flat.device.type == "cpu":
+            if flat.numel() and (int(flat.min()) < 0 or int(flat.max()) >= v):
+                raise O.OpError(f"{node.name}: indices out of range [0, {v})")
+            rows = self.blob.index_select(0, flat + base).float()
+        else:
+            ok = (flat >= 0) & (flat < v)
+            rows = self.blob.index_select(0, flat.clamp(0, v - 1) + base).float()
+            rows = torch.where(ok[:, None], rows, torch.zeros((), dtype=rows.dtype, device=rows.device))
+        g = rows.reshape(list(idx.shape) + [self.d])
+        if g.dim() < 2:
+            raise O.OpError(f"{node.name}: cannot sum a rank-{g.dim()} gather over axis 1")
+        return g.sum(dim=1)
+
+    def __call__(self, ctx, node, ins):
+        ins = [O.to_torch(v) for v in ins]
+        lead = ins[0] if self.lead else None
+        ids = ins[1:] if self.lead else ins
+        if self.use_hip and self.blob.is_cuda and all(i.is_cuda and i.dim() == 2 and i.dtype in (torch.int32, torch.int64)
+                                                      for i in ids):
+            from ..ops import hip
+            from .fused import _to_bf16
+            H = hip()
+            if self.split is not None:
+                sparse, hot = ids[0], self.split
+            else:
+                hot = [int(i.shape[1]) for i in ids]
+                same = all(i.shape[0] == ids[0].shape[0] and i.dtype == ids[0].dtype for i in ids)
+                sparse = torch.cat(ids, dim=1) if same and all(1 <= l for l in hot) else None
+            if sparse is not None and sparse.shape[1] == sum(hot):
+                B, T = int(sparse.shape[0]), int(sparse.shape[1])
+                lead_ok = lead is None or (lead.is_cuda and lead.dim() == 2 and tuple(lead.shape) == (B, self.d) and
+                                           lead.is_floating_point())
+                flat, feat = self.features(hot, sparse.device)
+                if lead_ok and H.embedding_bag_supported(B, T, self.d, flat, int(self.blob.shape[0]), lead is not None,
+                                                         sparse.dtype == torch.int64):
+                    dense = None if lead is None else _to_bf16(lead).contiguous()
+                    return [H.embedding_bag(sparse.contiguous(), self.blob, feat, flat, dense)]
+        if self.split is not None:
+            x = ids[0]
+            if x.dim() < 2:
+                raise O.OpError(f"{node.name}: cannot split a rank-{x.dim()} tensor along axis 1")
+            ids = list(torch.split(x, self.split, dim=1))       # (a wrong width raises, as the SplitV did)
+        parts = [self._rows(node, f, i) for f, i in enumerate(ids)]
+        if lead is not None:
+            parts = [lead.float().to(parts[0].device)] + parts
+        if self.concat:
+            y = torch.cat(parts, dim=1).reshape(-1, len(parts), self.d)
+        else:
+            y = torch.stack(parts, dim=1)
+        return [y.to(BF16) if self.use_hip and y.is_cuda else y]
+
+
+def _bag_term(g, c, ref, reader: Node):
+    """``ref`` = Sum(GatherV2(table const [V, D], ids, axis 0, batch_dims 0), axis=1, keep_dims=False),
+    both read once (the Sum by ``reader``) and not fetched -> (table, ids ref, [sum, gather]) or None."""
+    s = _node(g, ref)
+    if s is None or s.op != "Sum" or len(s.inputs) != 2 or bool(s.attr("keep_dims", False)) or \
+            c.only_consumer(s.name) is not reader:
+        return None
+    ax = _const_t(g, s.inputs[1])
+    if ax is None or ax.numel() != 1 or ax.is_floating_point() or int(ax.reshape(-1)[0]) != 1:
+        return None
+    ga = _node(g, s.inputs[0])
+    if ga is None or ga.op != "GatherV2" or len(ga.inputs) != 3 or int(ga.attr("batch_dims", 0)) != 0 or \
+            c.only_consumer(ga.name) is not s:
+        return None
+    table, gax = _const_t(g, ga.inputs[0]), _const_t(g, ga.inputs[2])
+    if table is None or table.dim() != 2 or not table.is_floating_point() or table.shape[0] < 1 or table.shape[1] < 1:
+        return None
+    if gax is None or gax.numel() != 1 or gax.is_floating_point() or int(gax.reshape(-1)[0]) != 0:
+        return None
+    if _const_t(g, ga.inputs[1]) is not None:
+        return None
+    return table, ga.inputs[1], [s, ga]
+
+
+def _common_split(g, c, id_refs, gathers):
+    """The ``SplitV(sparse, const size_splits, axis=1)`` whose outputs 0 .. F-1, in order, are
+    ``id_refs`` and feed nothing else -> (split node, sizes) or None."""
+    sp = g.nodes.get(id_refs[0][0])
+    if sp is None or sp.op != "SplitV" or len(sp.inputs) != 3 or sp.name in c.fetch_nodes:
+        return None
+    if [tuple(r) for r in id_refs] != [(sp.name, f) for f in range(len(id_refs))]:
+        return None
+    sizes, ax = _const_t(g, sp.inputs[1]), _const_t(g, sp.inputs[2])
+    if sizes is None or ax is None or ax.numel() != 1 or int(ax.reshape(-1)[0]) != 1 or sizes.is_floating_point():
+        return None
+    sizes = [int(v) for v in sizes.reshape(-1).tolist()]
+    if len(sizes) != len(id_refs) or any(s < 1 for s in sizes):
+        return None
+    readers = sorted(cn for cn, _p, _i in c.cons.get(sp.name, []))
+    if readers != sorted(ga.name for ga in gathers):
+        return None
+    return sp, sizes
+
+
+def fuse_embedding_bag(g, order, fed, fetch_refs, device, opts):
+    """``Pack([x_0?, e_0 .. e_{F-1}], axis=1)`` and ``Reshape(ConcatV2([..], axis=1), [-1, F0 + F, D])``
+    with every ``e_f`` a pooled row gather (``_bag_term``) of one width D, behind at most one leading
+    operand that is none -> ``_EmbeddingBag(x_0?, ids..)`` (class EmbeddingBagOp).  When the id
+    tensors are the outputs of one SplitV in order, the op reads its input and the SplitV goes."""
+    from .fused import _Ctx
+    c = _Ctx(g, order, fed, fetch_refs, device, opts)
+    for name in order:
+        out = g.nodes.get(name)
+        if out is None:
+            continue
+        concat = None
+        if out.op == "Pack" and int(out.attr("axis", 0)) == 1:
+            reader, operands = out, list(out.inputs)
+        elif out.op == "Reshape" and len(out.inputs) == 2:
+            concat = _node(g, out.inputs[0])
+            if concat is None or concat.op != "ConcatV2" or len(concat.inputs) < 2 or \
+                    c.only_consumer(concat.name) is not out:
+                continue
+            ax = _const_t(g, concat.inputs[-1])
+            if ax is None or ax.numel() != 1 or int(ax.reshape(-1)[0]) != 1:
+                continue
+            reader, operands = concat, list(concat.inputs[:-1])
+        else:
+            continue
+        if not operands:
+            continue
+        terms = [_bag_term(g, c, r, reader) for r in operands]
+        lead = terms[0] is None
+        if lead:
+            terms = terms[1:]
+        if not terms or any(t is None for t in terms):
+            continue
+        D = int(terms[0][0].shape[1])
+        if any(int(t[0].shape[1]) != D for t in terms):
+            continue
+        if concat is not None:
+            shp = _const_t(g, out.inputs[1])
+            if shp is None or [int(v) for v in shp.reshape(-1).tolist()] != [-1, len(operands), D]:
+                continue
+        id_refs = [t[1] for t in terms]
+        gathers = [t[2][1] for t in terms]
+        split = _common_split(g, c, id_refs, gathers)
+        interior = [n for t in terms for n in t[2]] + ([concat] if concat is not None else [])
+        impl = EmbeddingBagOp([t[0] for t in terms], None if split is None else split[1], lead, concat is not None,
+                              device, c.use_hip, out.name)
+        ins = ([operands[0]] if lead else []) + ([split[0].inputs[0]] if split is not None else id_refs)
+        if split is not None:
+            interior.append(split[0])
+        ctrl = []
+        for n in interior + [out]:
+            ctrl += [x for x in n.ctrl if x not in ctrl]
+        _remove(g, interior)
+        out.op = "_EmbeddingBag"
+        out.inputs = ins
+        out.ctrl = [x for x in ctrl if x in g.nodes]
+        out.attrs = {"_impl": impl}
+        out.value = None
+        c.refresh()
+
+
+def tril_pairs(f: int, k: int) -> List[int]:
+    """``i * f + j`` over ``np.tril_indices(f, k)`` (row-major: i ascending, then j <= i + k)."""
+    return [i * f + j for i in range(f) for j in range(0, min(i + k, f - 1) + 1)]
+
+
+class DotInteractionOp:
+    """``[Pad(] ConcatV2([dense, GatherV2(Reshape(BatchMatMul(Z, Z, adj_y), [-1, F F]), idx, axis=1)], axis=1)
+    [, [[0, 0], [0, pad]])]`` with ``idx`` the strict (``self_interaction`` False) or full lower
+    triangle in ``np.tril_indices`` order: on the GPU one ``dot_interaction`` launch
+    (kernels/interact.hip), fp32 accumulate and one rounding; the CPU and any input the kernel does
+    not take get the replaced nodes' semantics from torch."""
+
+    def __init__(self, f: int, self_interaction: bool, pad: int, device, use_hip: bool, name: str):
+        self.f, self.self_interaction, self.pad = int(f), bool(self_interaction), int(pad)
+        self.use_hip = use_hip
+        self.name = name
+        self.idx = to_device(torch.tensor(tril_pairs(self.f, 0 if self_interaction else -1), dtype=torch.int64), device)
+
+    def __call__(self, ctx, node, ins):
+        z, dense = O.to_torch(ins[0]), O.to_torch(ins[1])
+        nf = self.f
+        P = int(self.idx.numel())
+        if (self.use_hip and z.is_cuda and z.dim() == 3 and z.shape[1] == nf and z.is_floating_point() and
+                dense.is_cuda and dense.dim() == 2 and dense.shape[0] == z.shape[0] and dense.is_floating_point() and
+                dense.shape[1] >= 8):
+            from ..ops import hip
+            from .fused import _to_bf16
+            H = hip()
+            B, D, Dd = int(z.shape[0]), int(z.shape[2]), int(dense.shape[1])
+            if H.dot_interaction_supported(B, nf, D, Dd, self.pad, self.self_interaction):
+                y = H.dot_interaction(_to_bf16(z).contiguous(), _to_bf16(dense).contiguous(), self.self_interaction,
+                                      self.pad)
+                w = Dd + P + self.pad
+                return [y if y.shape[1] == w else y[:, :w]]
+        zf = z.float()
+        if zf.dim() < 2:
+            raise O.OpError(f"{node.name}: BatchMatMul of a rank-{zf.dim()} tensor")
+        zz = torch.matmul(zf, zf.transpose(-1, -2))
+        try:
+            flat = zz.reshape(-1, nf * nf)
+        except RuntimeError as e:
+            raise O.OpError(f"{node.name}: cannot reshape {list(zz.shape)} to [-1, {nf * nf}]: {e}") from None
+        pairs = flat.index_select(1, self.idx.to(flat.device))
+        y = torch.cat([dense.float().to(pairs.device), pairs], dim=1)
+        if self.pad:
+            y = F.pad(y, [0, self.pad])
+        return [y.to(BF16) if self.use_hip and y.is_cuda else y]
+
+
+def fuse_dot_interaction(g, order, fed, fetch_refs, device, opts):
+    """The pattern of class DotInteractionOp -> ``_DotInteraction(Z, dense)``.  Constants are read
+    by shape: ``idx`` must equal ``i F + j`` over ``np.tril_indices(F, -1)`` or ``(F, 0)`` exactly,
+    with F from the reshape's ``[-1, F F]``; the BatchMatMul has one operand twice, ``adj_y`` and no
+    ``adj_x``; a Pad is taken only as ``[[0, 0], [0, p]]`` with zeros.  The gather, the reshape, the
+    product and a concat that feeds a taken Pad are read once and not fetched."""
+    from .fused import _Ctx
+    c = _Ctx(g, order, fed, fetch_refs, device, opts)
+    for name in order:
+        cat = g.nodes.get(name)
+        if cat is None or cat.op != "ConcatV2" or len(cat.inputs) != 3:
+            continue
+        ax = _const_t(g, cat.inputs[2])
+        if ax is None or ax.numel() != 1 or ax.is_floating_point() or int(ax.reshape(-1)[0]) != 1:
+            continue
+        ga = _node(g, cat.inputs[1])
+        if ga is None or ga.op != "GatherV2" or len(ga.inputs) != 3 or int(ga.attr("batch_dims", 0)) != 0 or \
+                c.only_consumer(ga.name) is not cat:
+            continue
+        idx, gax = _const_t(g, ga.inputs[1]), _const_t(g, ga.inputs[2])
+        if idx is None or idx.is_floating_point() or idx.dim() != 1 or gax is None or gax.numel() != 1 or \
+                gax.is_floating_point() or int(gax.reshape(-1)[0]) != 1:
+            continue
+        rs = _node(g, ga.inputs[0])
+        if rs is None or rs.op != "Reshape" or len(rs.inputs) != 2 or c.only_consumer(rs.name) is not ga:
+            continue
+        shp = _const_t(g, rs.inputs[1])
+        if shp is None or shp.numel() != 2 or int(shp.reshape(-1)[0]) != -1:
+            continue
+        ff = int(shp.reshape(-1)[1])
+        f = math.isqrt(ff) if ff > 0 else 0
+        if f < 2 or f * f != ff:
+            continue
+        bm = _node(g, rs.inputs[0])
+        if bm is None or bm.op not in ("BatchMatMul", "BatchMatMulV2", "BatchMatMulV3") or len(bm.inputs) != 2 or \
+                bm.inputs[0] != bm.inputs[1] or bool(bm.attr("adj_x", False)) or not bool(bm.attr("adj_y", False)) or \
+                c.only_consumer(bm.name) is not rs or _const_t(g, bm.inputs[0]) is not None:
+            continue
+        got = [int(v) for v in idx.tolist()]
+        if got == tril_pairs(f, -1):
+            self_int = False
+        elif got == tril_pairs(f, 0):
+            self_int = True
+        else:
+            continue
+        interior, last, pad = [ga, rs, bm], cat, 0
+        p = c.only_consumer(cat.name)
+        if p is not None and p.op in ("Pad", "PadV2") and p.inputs[0] == (cat.name, 0):
+            pv = _const_t(g, p.inputs[1])
+            zero = p.op == "Pad" or (_scalar(g, p.inputs[2]) == 0.0)
+            if pv is not None and tuple(pv.shape) == (2, 2) and not pv.is_floating_point() and zero:
+                (b0, b1), (c0, c1) = pv.tolist()
+                if b0 == 0 and b1 == 0 and c0 == 0 and c1 >= 0:
+                    interior, last, pad = interior + [cat], p, int(c1)
+        impl = DotInteractionOp(f, self_int, pad, device, c.use_hip, last.name)
+        ctrl = []
+        for n in interior + [last]:
+            ctrl += [x for x in n.ctrl if x not in ctrl]
+        z_ref, dense_ref = bm.inputs[0], cat.inputs[0]
+        _remove(g, interior)
+        last.op = "_DotInteraction"
+        last.inputs = [z_ref, dense_ref]
+        last.ctrl = [x for x in ctrl if x in g.nodes]
+        last.attrs = {"_impl": impl}
+        last.value = None
+        c.refresh()
+
+
+def dlrm_passes():
+    """TFSERVE_DLRM=0 (read at every compile) removes the two passes: scripts/dlrm_bench.py's A/B in one build."""
+    return [] if os.environ.get("TFSERVE_DLRM", "1") == "0" else [fuse_embedding_bag, fuse_dot_interaction]
+
+
 def bert_passes():
     return [fuse_layernorm, fuse_embedding, fuse_window_attention, fold_window_layout, fuse_attention, fuse_key_mask]
 

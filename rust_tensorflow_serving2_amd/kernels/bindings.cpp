@@ -1214,6 +1214,97 @@ Tensor patch_tokens(const Tensor& x, const Tensor& table, const c10::optional<Te
   return y;
 }
 
+// out[b, F0 + f, :] = bf16(sum_l table_f[ids[b, first_f + l], :]); out[b, 0, :] = dense[b, :] when dense is given
+// ids: [B, T] int32 / int64, blob: [rows, D] bf16, feat: [F, 4] int64 on the device, features: the same F x 4
+// values on the host (checked here; the op builds both from one list), dense: [B, D] bf16
+Tensor embedding_bag(const Tensor& ids, const Tensor& blob, const Tensor& feat, const std::vector<int64_t>& features,
+                     const c10::optional<Tensor>& dense, const c10::optional<Tensor>& out) {
+  TORCH_CHECK(ids.scalar_type() == at::kInt || ids.scalar_type() == at::kLong, "embedding_bag: ids has dtype ",
+              ids.scalar_type(), ", expected int32 or int64");
+  need(ids, ids.scalar_type(), "ids");
+  need(blob, at::kBFloat16, "blob");
+  need(feat, at::kLong, "feat");
+  TORCH_CHECK(ids.dim() == 2, "embedding_bag: ids must be [B, T]");
+  TORCH_CHECK(blob.dim() == 2, "embedding_bag: blob must be [rows, D]");
+  const int64_t B = ids.size(0), T = ids.size(1), rows = blob.size(0), D = blob.size(1);
+  TORCH_CHECK(feat.dim() == 2 && feat.size(0) >= 1 && feat.size(1) == 4, "embedding_bag: feat must be [F, 4]");
+  const int64_t F = feat.size(0);
+  TORCH_CHECK(int64_t(features.size()) == F * 4, "embedding_bag: features has ", features.size(),
+              " values, feat has ", F * 4);
+  TORCH_CHECK(D % 8 == 0 && D >= tfsk::kEmbagMinD && D <= tfsk::kEmbagMaxD, "embedding_bag: D must be a multiple of 8 in [",
+              tfsk::kEmbagMinD, ", ", tfsk::kEmbagMaxD, "], got ", D);
+  TORCH_CHECK(T >= 1, "embedding_bag: ids has no columns");
+  for (int64_t f = 0; f < F; ++f) {
+    const int64_t* p = features.data() + f * 4;
+    TORCH_CHECK(p[3] >= 1 && p[3] <= tfsk::kEmbagMaxHot, "embedding_bag: feature ", f, " has hotness ", p[3],
+                ", supported 1 .. ", tfsk::kEmbagMaxHot);
+    TORCH_CHECK(tfsk::embedding_bag_feature_ok(p[0], p[1], p[2], p[3], rows, T, D), "embedding_bag: feature ", f,
+                " (row base ", p[0], ", rows ", p[1], ", first slot ", p[2], ", hotness ", p[3],
+                ") does not fit the blob [", rows, ", ", D, "] / ids [., ", T, "], or its table is 2 GiB or more");
+    TORCH_CHECK((p[0] * D * 2) % 16 == 0, "embedding_bag: table ", f, " must be 16-byte aligned");
+  }
+  TORCH_CHECK(aligned16(ids), "embedding_bag: ids must be 16-byte aligned");
+  TORCH_CHECK(aligned16(blob), "embedding_bag: blob must be 16-byte aligned");
+  const uint16_t* dp = nullptr;
+  if (dense.has_value()) {
+    need(*dense, at::kBFloat16, "dense");
+    TORCH_CHECK(dense->dim() == 2 && dense->size(0) == B && dense->size(1) == D, "embedding_bag: dense must be [", B,
+                ", ", D, "]");
+    TORCH_CHECK(aligned16(*dense), "embedding_bag: dense must be 16-byte aligned");
+    dp = bf16p(*dense);
+  }
+  const int64_t F0 = dp != nullptr ? 1 : 0;
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(ids.device());
+  Tensor y = out.has_value() ? *out : torch::empty({B, F0 + F, D}, blob.options());
+  need(y, at::kBFloat16, "out");
+  TORCH_CHECK(y.numel() == B * (F0 + F) * D, "embedding_bag: out has the wrong size");
+  TORCH_CHECK(aligned16(y), "embedding_bag: out must be 16-byte aligned");
+  const bool i64 = ids.scalar_type() == at::kLong;
+  TORCH_CHECK(tfsk::embedding_bag_supported(B, T, D, F, F0, i64),
+              "embedding_bag: ids, dense and out must be smaller than 2 GiB, with at most 65535 rows per sample");
+  check(tfsk::embedding_bag_launch(ids.data_ptr(), i64, bf16p(blob), feat.data_ptr<int64_t>(), dp, bf16p_mut(y), B, T,
+                                   D, F, cur_stream(ids)),
+        "embedding_bag");
+  return y;
+}
+
+// out[b] = [dense[b] | z_i . z_j in tril order | zeros], out: [B, ceil8(Dd + pairs + pad)]
+Tensor dot_interaction(const Tensor& z, const c10::optional<Tensor>& dense, bool self_interaction, int64_t pad,
+                       const c10::optional<Tensor>& out) {
+  need(z, at::kBFloat16, "z");
+  TORCH_CHECK(z.dim() == 3, "dot_interaction: z must be [B, F, D]");
+  const int64_t B = z.size(0), F = z.size(1), D = z.size(2);
+  TORCH_CHECK(F >= 2 && F <= tfsk::kInteractMaxF, "dot_interaction: supports 2 <= F <= ", tfsk::kInteractMaxF,
+              ", got F = ", F);
+  TORCH_CHECK(D % 32 == 0 && D >= 32 && D <= tfsk::kInteractMaxD, "dot_interaction: D must be a multiple of 32 in [32, ",
+              tfsk::kInteractMaxD, "], got ", D);
+  TORCH_CHECK(pad >= 0, "dot_interaction: pad must be >= 0, got ", pad);
+  TORCH_CHECK(aligned16(z), "dot_interaction: z must be 16-byte aligned");
+  int64_t Dd = 0;
+  const uint16_t* dp = nullptr;
+  if (dense.has_value()) {
+    need(*dense, at::kBFloat16, "dense");
+    TORCH_CHECK(dense->dim() == 2 && dense->size(0) == B, "dot_interaction: dense must be [", B, ", Dd]");
+    Dd = dense->size(1);
+    TORCH_CHECK(Dd >= 8 && Dd % 8 == 0, "dot_interaction: Dd % 8 != 0 (Dd = ", Dd, ")");
+    TORCH_CHECK(aligned16(*dense), "dot_interaction: dense must be 16-byte aligned");
+    dp = bf16p(*dense);
+  }
+  const int64_t Wp = tfsk::dot_interaction_width(F, Dd, pad, self_interaction);
+  TORCH_CHECK(Wp - Dd <= tfsk::kInteractMaxTail, "dot_interaction: pairs + pad exceed ", tfsk::kInteractMaxTail,
+              " columns");
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(z.device());
+  Tensor y = out.has_value() ? *out : torch::empty({B, Wp}, z.options());
+  need(y, at::kBFloat16, "out");
+  TORCH_CHECK(y.numel() == B * Wp, "dot_interaction: out has the wrong size (expected [", B, ", ", Wp, "])");
+  TORCH_CHECK(aligned16(y), "dot_interaction: out must be 16-byte aligned");
+  TORCH_CHECK(tfsk::dot_interaction_supported(B, F, D, Dd, pad, self_interaction),
+              "dot_interaction: operands must be smaller than 2 GiB");
+  check(tfsk::dot_interaction_launch(bf16p(z), dp, bf16p_mut(y), B, F, D, Dd, pad, self_interaction, cur_stream(z)),
+        "dot_interaction");
+  return y;
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -1375,6 +1466,41 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("x"), py::arg("table"), py::arg("out") = py::none());
   m.def("patch_tokens_supported", [](int64_t b, int64_t p, int64_t c) { return tfsk::patch_tokens_supported(b, p, c); },
         "whether patch_tokens takes [B, P, C]: C % 8 == 0 and every operand below 2 GiB");
+  m.def("embedding_bag", &embedding_bag, "pooled row gathers of every sparse feature (+ the dense row) in one launch",
+        py::arg("ids"), py::arg("blob"), py::arg("feat"), py::arg("features"), py::arg("dense") = py::none(),
+        py::arg("out") = py::none());
+  m.def("embedding_bag_supported",
+        [](int64_t b, int64_t t, int64_t d, const std::vector<int64_t>& features, int64_t rows, bool dense, bool ids64) {
+          if (features.empty() || features.size() % 4 != 0) return false;
+          const int64_t F = int64_t(features.size() / 4);
+          if (!tfsk::embedding_bag_supported(b, t, d, F, dense ? 1 : 0, ids64)) return false;
+          for (int64_t f = 0; f < F; ++f) {
+            const int64_t* p = features.data() + f * 4;
+            if (!tfsk::embedding_bag_feature_ok(p[0], p[1], p[2], p[3], rows, t, d)) return false;
+          }
+          return true;
+        },
+        py::arg("B"), py::arg("T"), py::arg("D"), py::arg("features"), py::arg("rows"), py::arg("dense") = false,
+        py::arg("ids64") = true,
+        "whether embedding_bag takes ids [B, T] and a blob [rows, D] with the flat (row base, V, first slot, hotness) "
+        "features: D % 8 == 0 in [8, 1024], hotness 1 .. 64, every table and operand below 2 GiB");
+  m.def("dot_interaction", &dot_interaction, "dense | pairwise dots in tril order | zero tail, one launch",
+        py::arg("z"), py::arg("dense") = py::none(), py::arg("self_interaction") = false, py::arg("pad") = 0,
+        py::arg("out") = py::none());
+  m.def("dot_interaction_supported",
+        [](int64_t b, int64_t f, int64_t d, int64_t dd, int64_t pad, bool self_interaction) {
+          return tfsk::dot_interaction_supported(b, f, d, dd, pad, self_interaction);
+        },
+        py::arg("B"), py::arg("F"), py::arg("D"), py::arg("Dd") = 0, py::arg("pad") = 0,
+        py::arg("self_interaction") = false,
+        "whether dot_interaction takes Z [B, F, D] with Dd dense columns: 2 <= F <= 32, D % 32 == 0 in [32, 256], "
+        "Dd % 8 == 0");
+  m.def("dot_interaction_width",
+        [](int64_t f, int64_t dd, int64_t pad, bool self_interaction) {
+          return tfsk::dot_interaction_width(f, dd, pad, self_interaction);
+        },
+        py::arg("F"), py::arg("Dd") = 0, py::arg("pad") = 0, py::arg("self_interaction") = false,
+        "row stride of dot_interaction's output: ceil8(Dd + pairs + pad)");
   m.def("splitk_counters_set_owner", [](int64_t owner) { tfsk::splitk_counters_set_owner(owner); },
         "tag the split-K counter slices this thread's captures take (0 = none)");
   m.def("splitk_counters_release", [](int64_t owner) { return tfsk::splitk_counters_release(owner); },

@@ -361,4 +361,33 @@ hipError_t window_attention_launch(const uint16_t* qkv, const float* bias, const
                                    int S, int H, int nW, float scale, int Hf, int Wf, int ws, int shift,
                                    hipStream_t stream);
 
+// Embedding bag (kernels/embag.hip): out[b][F0 + f] = bf16(sum_{l < L_f} table_f[ids[b][first_f + l]]) for
+// every feature in one launch; ids [B][T] int32 / int64, blob [rows][D] bf16 (all tables), feat [F][4] int64
+// on the device = (first blob row, V_f, first_f, L_f) per feature, dense [B][D] bf16 or null (copied to row 0:
+// F0 = 1), out [B][F0 + F][D] bf16.  An id outside [0, V_f) adds zeros.  D % 8 == 0, 8 <= D <= 1024,
+// 1 <= L_f <= 64, every table and every other operand 16-B aligned and below 2 GiB (the blob may be larger).
+// The launcher trusts feat: the caller checks each feature with embedding_bag_feature_ok first.
+constexpr int kEmbagMinD = 8;
+constexpr int kEmbagMaxD = 1024;
+constexpr int kEmbagMaxHot = 64;
+bool embedding_bag_supported(int64_t B, int64_t T, int64_t D, int64_t F, int64_t F0, bool ids64);
+bool embedding_bag_feature_ok(int64_t row_base, int64_t V, int64_t first, int64_t L, int64_t rows, int64_t T,
+                              int64_t D);
+hipError_t embedding_bag_launch(const void* ids, bool ids64, const uint16_t* blob, const int64_t* feat,
+                                const uint16_t* dense, uint16_t* out, int64_t B, int64_t T, int64_t D, int64_t F,
+                                hipStream_t stream);
+
+// Dot interaction (kernels/interact.hip): out[b] = [dense[b] | z_i . z_j in np.tril_indices(F, self ? 0 : -1)
+// order | zeros], Z [B][F][D] bf16, dense [B][Dd] bf16 or null (Dd = 0), out [B][Wp] bf16 with
+// Wp = dot_interaction_width = ceil8(Dd + pairs + pad), every column written.  2 <= F <= 32, D % 32 == 0,
+// 32 <= D <= 256, Dd % 8 == 0, Wp - Dd <= kInteractMaxTail, operands 16-B aligned and below 2 GiB.
+constexpr int kInteractMaxF = 32;
+constexpr int kInteractMaxD = 256;
+constexpr int kInteractMaxTail = 1024;
+int64_t dot_interaction_pairs(int64_t F, bool self);
+int64_t dot_interaction_width(int64_t F, int64_t Dd, int64_t pad, bool self);
+bool dot_interaction_supported(int64_t B, int64_t F, int64_t D, int64_t Dd, int64_t pad, bool self);
+hipError_t dot_interaction_launch(const uint16_t* z, const uint16_t* dense, uint16_t* out, int64_t B, int64_t F,
+                                  int64_t D, int64_t Dd, int64_t pad, bool self, hipStream_t stream);
+
 }  // namespace tfsk

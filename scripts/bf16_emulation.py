@@ -35,6 +35,7 @@ same ops rounded, _WindowAttention in _Attention's place); `--swin-bias-std` ove
     python scripts/bf16_emulation.py --family convnext --seeds 0 1 2 --trials 3
     python scripts/bf16_emulation.py --family vit --image-size 224 --seeds 0 1 2 --trials 2
     python scripts/bf16_emulation.py --family swin --image-size 224 --seeds 0 1 2 --trials 2
+    python scripts/bf16_emulation.py --family dlrm --batch 64 --seeds 0 1 2 --trials 2 [--emb-scale 1.0]
 """
 import argparse
 import os
@@ -88,9 +89,46 @@ def emulate(program, trial, ops=ROUNDED):
     program.steps = steps
 
 
+DLRM_ROUNDED = ("_FusedMatMul", "_EmbeddingBag", "_DotInteraction")
+
+
+def dlrm_main(a):
+    """--family dlrm: models/dlrm.py's ``--dlrm-config`` at ``--vocab-cap`` and ``--emb-scale``; GEMM weights, the
+    tables and every fused op's output rounded to bf16.  Prints, per input seed, the batch's fp32 logits'
+    spread (max - min over the batch) and the worst |logit error| / spread."""
+    from rust_tensorflow_serving2_amd.models import dlrm
+    scale = dlrm.EMB_SCALE if a.emb_scale is None else a.emb_scale
+    path = os.path.join(tempfile.mkdtemp(), "1")
+    dlrm.export(path, a.dlrm_config, seed=a.model_seed, vocab_cap=a.vocab_cap, emb_scale=scale)
+    ref = Servable("m", 1, path, ServableOptions(device="cpu"))
+    emu = Servable("m", 1, path, ServableOptions(device="cpu", fuse=True))
+    outs, trial = ["logits", "probabilities"], [0]
+    program = emu.runner("serving_default", ["dense", "sparse"], outs).program
+    emulate(program, trial, DLRM_ROUNDED)
+    for _fn, node, _i, _o in program.steps:
+        if node.op == "_EmbeddingBag":
+            node.attrs["_impl"].blob = bf16(node.attrs["_impl"].blob)
+    print(a.dlrm_config, "vocab cap", a.vocab_cap, "embedding scale", scale, "batch", a.batch)
+    for s in a.seeds:
+        dense, sparse = dlrm.random_inputs(a.dlrm_config, a.batch, seed=s, vocab_cap=a.vocab_cap, ends=True)
+        lg = ref.run("serving_default", {"dense": dense, "sparse": sparse}, outs)["logits"].astype(np.float64).ravel()
+        spread = lg.max() - lg.min()
+        print(f"{a.dlrm_config} input seed {s} logits {lg.min():.3f} .. {lg.max():.3f} spread (max - min over the "
+              f"batch) {spread:.4f}")
+        for t in range(a.trials):
+            trial[0] = t
+            le = emu.run("serving_default", {"dense": bf16(torch.from_numpy(dense)).numpy(), "sparse": sparse},
+                         outs)["logits"].astype(np.float64).ravel()
+            print(f"    trial {t} emulated worst |logit error| {np.abs(le - lg).max():.5f} = "
+                  f"{100 * np.abs(le - lg).max() / spread:.2f} % of the spread")
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
-    ap.add_argument("--family", default="mobilenet", choices=["mobilenet", "resnext", "efficientnet", "convnext", "vit", "swin"],
+    ap.add_argument("--dlrm-config", default="dlrm_criteo")
+    ap.add_argument("--vocab-cap", type=int, default=1000)
+    ap.add_argument("--emb-scale", type=float)
+    ap.add_argument("--family", default="mobilenet", choices=["mobilenet", "resnext", "efficientnet", "convnext", "vit", "swin", "dlrm"],
                     help="resnext: ResNeXt-50 32x4d at full width (tests/test_resnext_gpu.py's model); efficientnet: "
                          "EfficientNet-B0 at full width (tests/test_efficientnet_gpu.py's model); convnext: ConvNeXt-T "
                          "at full width and depth (tests/test_convnext_gpu.py's model); vit: ViT-S/16 "
@@ -111,6 +149,8 @@ def main():
     ap.add_argument("--swin-bias-std", type=float)
     ap.add_argument("--patch", type=int, default=16)
     a = ap.parse_args()
+    if a.family == "dlrm":
+        return dlrm_main(a)
     if a.gated_gain is not None:
         mobilenet.V3_GATED_PROJECT_GAIN = dict(mobilenet.V3_GATED_PROJECT_GAIN, **{a.version: a.gated_gain})
     if a.expand_gain is not None:

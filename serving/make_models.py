@@ -5,7 +5,7 @@ The reference downloads ``resnet_v2_fp32_savedmodel_NHWC`` and copies version
 Offline, we write random-init SavedModels of the same architectures in the
 same ``<root>/<name>/<version>/`` layout:
 
-    python serving/make_models.py --root serving/models [--models resnet,resnet_v2,resnext50,mobilenet,mobilenet_v2,mobilenet_v3_large,mobilenet_v3_small,efficientnet_b0,convnext_tiny,vit_b16,swin_tiny,bert,half_plus_two]
+    python serving/make_models.py --root serving/models [--models resnet,resnet_v2,resnext50,mobilenet,mobilenet_v2,mobilenet_v3_large,mobilenet_v3_small,efficientnet_b0,convnext_tiny,vit_b16,swin_tiny,bert,dlrm,half_plus_two]
 
 * ``resnet``        ResNet-50 v1.5 (NHWC, alias "input", outputs classes/probabilities)
 * ``resnet_v2``     ResNet-50 v2 pre-activation (the fetch.sh model's architecture)
@@ -18,6 +18,8 @@ same ``<root>/<name>/<version>/`` layout:
 * ``vit_b16``       ViT-B/16 224 (TF layout: patch conv, class token by Tile + ConcatV2, 12 pre-LN blocks, S = 197)
 * ``swin_tiny``     Swin-T 224 (TF layout: 4x4 patch conv, window 7, tf.roll shifted windows, packed QKV, patch merging)
 * ``bert``          BERT-base seq 128 (input_ids / input_mask / segment_ids)
+* ``dlrm``          DLRM, Criteo layout (13 dense + 26 sparse features, D = 128, tables capped at 40000 rows: 198 MB;
+                    Predict dense / sparse, Classify and Regress over tf.Examples)
 * ``half_plus_two`` TF Serving's canonical test model
 
 and ``example.jpg`` (a synthetic 224x224 RGB image).
@@ -68,6 +70,9 @@ def main(argv=None):
         elif m == "bert":
             from rust_tensorflow_serving2_amd.models import bert
             bert.export(out, bert.BertConfig(), seed=args.seed)
+        elif m == "dlrm":
+            from rust_tensorflow_serving2_amd.models import dlrm
+            dlrm.export(out, "dlrm_criteo", seed=args.seed)
         elif m == "half_plus_two":
             half_plus_two.export(out)
         else:
