@@ -422,7 +422,8 @@ class FusedDepthwiseConv(_Window):
     """DepthwiseConv2dNative (channel multiplier 1)(+folded BN/bias)(+act).
     The filter stays fp32 on both paths: [KH][KW][C], which the kernel reads as
     [KH*KW][C] (9 C floats for a 3x3: rounding it to bf16 would cost 2^-9
-    relative error for no saving)."""
+    relative error for no saving).  A geometry whose last window holds padding
+    alone, which the kernel does not take, runs with torch on the device."""
 
     MAX_K = 7                       # kernels/dwconv.hip kMaxTaps
 
@@ -453,6 +454,10 @@ class FusedDepthwiseConv(_Window):
         ho, wo = self.out_hw(h, w, (pt, pb, pl, pr))
         if not self.use_hip:
             return [_ref_act(self._torch(x, (pt, pb, pl, pr)), self.act).contiguous()]
+        if (ho - 1) * self.sh - pt >= h or (wo - 1) * self.sw - pl >= w:
+            # an EXPLICIT bottom / right pad as large as the filter: the last window holds padding alone,
+            # which dwconv2d refuses; TF computes it (act(bias) there), so torch does, with one bf16 store
+            return [_ref_act(self._torch(x, (pt, pb, pl, pr)), self.act).to(BF16).contiguous()]
         from ..ops import ACT, hip, tuned_choice
         H = hip()
         x = _to_bf16(x).contiguous()
@@ -483,8 +488,8 @@ class FusedDepthwiseLN:
     (kernels/dwln.hip), the conv result in fp32 up to the one rounding of the
     normalised output.  It owns the two ops it replaces (``dw``, ``ln``: their
     weights are its weights) and runs them as they were for an input that is
-    not NHWC with C channels, for a shape the kernel does not take, and under
-    ``TFSERVE_DWLN=0`` (A/B only)."""
+    not NHWC with C channels, for a shape the kernel does not take (a last
+    window of padding alone among them), and under ``TFSERVE_DWLN=0`` (A/B only)."""
 
     children = ("dw", "ln")             # placement.weight_refs
 
@@ -517,8 +522,10 @@ class FusedDepthwiseLN:
             return [F.layer_norm(y, (self.c,), gamma.to(x.device), beta.to(x.device), self.eps).contiguous()]
         from ..ops import hip
         H = hip()
+        # (a last window of bottom / right padding alone, an EXPLICIT pad of 7 or more, is refused by
+        # dwconv_ln as by dwconv2d: the pair's depthwise op computes it with torch)
         if (os.environ.get("TFSERVE_DWLN", "1") == "0" or not x.is_cuda or ho < 1 or wo < 1 or
-                not H.dwconv_ln_supported(n, ho, wo, self.c, 7, 7, 1, 1)):
+                ho - 1 - pt >= h or wo - 1 - pl >= w or not H.dwconv_ln_supported(n, ho, wo, self.c, 7, 7, 1, 1)):
             return self._pair(ctx, node, x)
         x = _to_bf16(x).contiguous()
         out = torch.empty((n, ho, wo, self.c), device=x.device, dtype=BF16)

@@ -15,16 +15,24 @@ The unpackers invert the documented weight layouts: they return the logical
 weights and, separately, everything else the packed tensor holds (the padding),
 which must be exactly zero.
 
-The case lists at the bottom are shared by test_fused_ops_cpu.py (an ideal fp32
-emulation stays inside the bound, each mutant is rejected) and
-test_fused_ops_gpu.py (the op classes on the kernels)."""
+The case lists are shared by test_fused_ops_cpu.py (an ideal fp32 emulation
+stays inside the bound, each mutant is rejected) and test_fused_ops_gpu.py (the
+op classes on the kernels).  The second half does the same for the op classes
+of the later model families, with the bounds of their own kernel modules."""
 import math
 
 import torch
 import torch.nn.functional as F
 
+import dwconv_bounds as db
+import dwln_bounds as lb
+import interact_bounds as ib
 import kernel_bounds as kb
+import se_bounds as sb
+import swish_bounds as wb
+import wattn_bounds as ab
 from kernel_bounds import BF, rnd
+from patch_tokens_bounds import reference as pt_reference
 
 
 # ---------------------------------------------------------------- TF padding
@@ -267,3 +275,237 @@ MATMUL_KN = [(64, 13), (72, 13), (20, 13)]
 def matmul_inputs(m, k, n, seed=0):
     x, w_nk, b, r = kb.gemm_inputs(m, n, k, seed=seed + k + n)
     return x, w_nk.float().t().contiguous(), q6(b), r
+
+
+# ================================================================ the ops added since MobileNet
+# Depthwise conv, depthwise 7x7 + LayerNorm, patch tokens, windowed attention,
+# embedding bag and dot interaction: (ref, bound) for what the op classes take,
+# each bound from the module that holds the kernel's (dwconv_bounds, se_bounds,
+# swish_bounds, dwln_bounds, wattn_bounds, interact_bounds, and the patch-token
+# bound of patch_tokens_bounds).
+DW_ACTS = ("none", "relu", "relu6", "hard_swish", "swish")
+
+
+def dw_parts_tf(x, w_hwc, bias, strides, padding, pads=(0, 0, 0, 0)):
+    """(pre, mag, taps) of a depthwise conv + bias in TF terms (dwconv_bounds.dw_parts under tf_pads)."""
+    kh, kw, _c = w_hwc.shape
+    p = tf_pads(x.shape[1], x.shape[2], kh, kw, strides[0], strides[1], padding, pads)
+    pre, mag = db.dw_parts(x, w_hwc, bias, tuple(strides), p)
+    return pre, mag, kh * kw
+
+
+def dw_epilogue(pre, mag, taps, act):
+    """(ref, bound) of one of DW_ACTS on the parts: se_bounds for hard-swish, swish_bounds for swish, and
+    dwconv_bounds.dw_ref's own line for none / relu / relu6 (test_fused_ops_cpu.py holds the two equal)."""
+    if act in ("hard_swish", "swish"):
+        return (sb.hard_swish_dw if act == "hard_swish" else wb.swish_dw)(pre, mag, taps)
+    ref = db.act64x(act, pre)
+    return ref, kb.out_bound(ref, (taps + 2) * kb.E * mag, out_f32=False)
+
+
+def dw_ref(x, w_hwc, bias, strides, padding, pads=(0, 0, 0, 0), act="none"):
+    """FusedDepthwiseConv: an HWC fp32 filter, (sh, sw), TF padding, one of DW_ACTS."""
+    return dw_epilogue(*dw_parts_tf(x, w_hwc, bias, strides, padding, pads), act)
+
+
+def dwln_ref(x, w_hwc, bias, gamma, beta, eps, padding, pads=(0, 0, 0, 0), fused=True):
+    """FusedDepthwiseLN.  gamma / beta: [C] or one element each.
+
+    fused: the kernel keeps the conv value in fp32, dwln_bounds.dwln_ref.
+    Not fused (FusedDepthwiseLN._pair): dwconv2d stores bf16(v) first, with v the
+    fp32 conv value of dwconv_bounds, |v - pre| <= acc = (49 + 2) E mag.  The
+    LayerNorm therefore reads z with |z - pre| <= 2^-8 (|pre| + acc) + acc, which
+    is dwconv_bounds' own out_bound(pre, acc); that is the `dz` handed to
+    kernel_bounds.layernorm_ref, whose bound then covers the LayerNorm kernel's
+    statistics, affine and store as it does for linear_ln's accumulation error."""
+    c = w_hwc.shape[2]
+    p = tf_pads(x.shape[1], x.shape[2], 7, 7, 1, 1, padding, pads)
+    gamma, beta = gamma.reshape(-1).expand(c), beta.reshape(-1).expand(c)
+    if fused:
+        return lb.dwln_ref(x, w_hwc, bias, gamma, beta, eps, p)
+    pre, mag = db.dw_parts(x, w_hwc, bias, 1, p)
+    return kb.layernorm_ref(pre, gamma, beta, eps, dz=kb.out_bound(pre, (lb.TAPS + 2) * kb.E * mag, False))
+
+
+def patch_tokens_ref(x, cls, pos, batch):
+    """PatchTokens: concat([cls repeated batch times, reshape(x, [-1, P, C])], 1) + pos, pos [P + 1, C] or
+    [1, P + 1, C].  The bound is patch_tokens_bounds.reference's, E |ref| + ulp_bf16(|ref| (1 + E)) / 2, on
+    the exact fp64 table.  Row 0 gets one more term: PatchTokens.__init__ forms cls + pos[0] with ONE fp32
+    addition before the kernel sees it, so the table row the kernel rounds is off by at most half an ulp of
+    fp32, 2^-24 |cls + pos[0]|."""
+    c = cls.numel()
+    pos64 = kb.d(pos).reshape(-1, c)
+    table = pos64.clone()
+    table[0] += kb.d(cls).reshape(c)
+    xr = x.reshape(-1, pos64.shape[0] - 1, c)
+    assert xr.shape[0] == batch, (tuple(x.shape), batch)
+    ref, bound = pt_reference(xr, table)
+    bound[:, 0] += kb.U_F32 * ref[:, 0].abs()
+    return ref, bound
+
+
+def wattn_ref(qkv, bias, mask, heads, scale, grid=None):
+    """WindowAttentionOp.  qkv [R, 3 H D]; grid None: rows in window order, mask window bw % nW;
+    grid (Hf, Wf, ws, shift): rows in image order.  Partition, cyclic shift and reverse are written
+    out here (TF's Roll(-shift) -> window partition ... window reverse -> Roll(+shift))."""
+    if grid is None:
+        return ab.window_attention_ref(qkv, bias, mask, heads, scale)
+    hf, wf, ws, shift = grid
+    b = qkv.shape[0] // (hf * wf)
+
+    def part(t):
+        t = torch.roll(t.reshape(b, hf, wf, -1), (-shift, -shift), (1, 2))
+        return t.reshape(b, hf // ws, ws, wf // ws, ws, -1).transpose(2, 3).reshape(b * hf * wf, -1)
+
+    def back(t):
+        t = t.reshape(b, hf // ws, wf // ws, ws, ws, -1).transpose(2, 3).reshape(b, hf, wf, -1)
+        return torch.roll(t, (shift, shift), (1, 2)).reshape(b * hf * wf, -1)
+    ref, bound = ab.window_attention_ref(part(qkv), bias, mask, heads, scale)
+    return back(ref), back(bound)
+
+
+def bag_ref(ids, tables, hot, dense=None):
+    """EmbeddingBagOp: ids [B, T] or a list of [B, L_f]; tables fp32 [V_f, D] holding bf16 values (so the
+    op's one rounding of the blob is exact); -> (ref, bound) [B, F0 + F, D]."""
+    if isinstance(ids, (list, tuple)):
+        ids = torch.cat([i.long() for i in ids], 1)
+    for t in tables:
+        assert torch.equal(t.to(BF).float(), t.float())
+    return ib.embag_ref(ids, [t.to(BF) for t in tables], hot, None if dense is None else dense.to(BF))
+
+
+def tril_order(f, self_interaction):
+    """np.tril_indices(f, 0 | -1) spelled out: i ascending, then j ascending, j <= i (j < i)."""
+    return [(i, j) for i in range(f) for j in range(f) if (j <= i if self_interaction else j < i)]
+
+
+def interact_ref(z, dense, self_interaction, pad):
+    """DotInteractionOp: [dense | z_i . z_j over tril_order | pad zeros], width Dd + P + pad exactly."""
+    k = 0 if self_interaction else -1
+    assert ib.tril_pairs(z.shape[1], k) == tril_order(z.shape[1], self_interaction)
+    ref, bound = ib.interact_ref(z, dense, k, pad)
+    w = dense.shape[1] + len(tril_order(z.shape[1], self_interaction)) + pad
+    assert not ref[:, w:].any() and not bound[:, w:].any()
+    return ref[:, :w], bound[:, :w]
+
+
+# ---------------------------------------------------------------- shared cases
+# (kh, kw), (n, h, w, c), (sh, sw), padding, pads: a few images of at most 20 x 23, more than one
+# strip / block row, odd sizes, C = 8 .. 96 (the 5x5 strip kernel handles 4 channels a thread, the others 8).
+def _dw(k, img, s, padding="SAME", pads=(0, 0, 0, 0)):
+    return (k, img, s, padding, pads)
+
+
+DW_EVEN, DW_ODD = (2, 20, 22, 24), (2, 19, 23, 24)
+DW_CASES = [_dw(k, img, (s, s)) for k in ((3, 3), (5, 5), (7, 7), (3, 5)) for img in (DW_EVEN, DW_ODD) for s in (1, 2)]
+DW_CASES += [_dw(k, DW_ODD, (1, 1), "VALID") for k in ((3, 3), (5, 5), (7, 7), (3, 5))]
+DW_CASES += [_dw(k, (3, 9, 11, 96), (s, s), "EXPLICIT", (2, 0, 1, 3)) for k in ((3, 3), (5, 5), (3, 5)) for s in (1, 2)]
+DW_CASES += [_dw((3, 3), (3, 9, 11, 96), (s, s), "EXPLICIT", (2, 0, 1, 2)) for s in (1, 2)]      # the strip kernel
+DW_CASES += [_dw(k, DW_EVEN, (1, 2)) for k in ((3, 3), (5, 5), (3, 5))]
+DW_CASES += [_dw((7, 7), (3, 4, 5, 8), (1, 1)), _dw((5, 5), (3, 2, 3, 8), (2, 2)), _dw((3, 3), (3, 2, 2, 40), (1, 1))]
+
+
+def dw_case_id(case):
+    (kh, kw), (n, h, w, c), (sh, sw), padding, pads = case
+    return f"{kh}x{kw}-{n}x{h}x{w}x{c}-s{sh}{sw}-{padding.lower()}" + ("".join(map(str, pads)) if any(pads) else "")
+
+
+def dw_kernel(case):
+    """Which kernel FusedDepthwiseConv launches: the tuned_choice key's first element, None = the generic one."""
+    (kh, kw), _img, (sh, sw), _p, _pads = case
+    if sh == sw and sh in (1, 2) and (kh, kw) in ((3, 3), (5, 5)):
+        return "dwconv" if kh == 3 else "dwconv5x5"
+    return None
+
+
+def dw_padding_only_tail(case):
+    """The last window starts beyond the image (a bottom / right pad as large as the filter): TF computes
+    act(bias) there; kernels/dwconv.hip's binding refuses the launch."""
+    (kh, kw), (_n, h, w, _c), (sh, sw), padding, pads = case
+    p = tf_pads(h, w, kh, kw, sh, sw, padding, pads)
+    ho, wo = out_hw(h, w, kh, kw, sh, sw, p)
+    return (ho - 1) * sh - p[0] >= h or (wo - 1) * sw - p[2] >= w
+
+
+def dw_case_inputs(case):
+    """x bf16-valued fp32 NHWC, an fp32 HWC filter (NOT bf16-valued: the op keeps it fp32), an fp32 bias.
+    The pre-activations spread over about +-5: both clamps of relu6 / hard-swish and swish's tail."""
+    (kh, kw), (n, h, w, c), _s, _p, _pads = case
+    seed = 100 * kh + 10 * kw + h + c
+    x = rnd(n, h, w, c, scale=2.0, seed=seed).to(BF).float()
+    wt = rnd(kh, kw, c, scale=2.0 / math.sqrt(kh * kw), seed=seed + 1)
+    return x, wt, rnd(c, scale=1.5, seed=seed + 2)
+
+
+# (n, h, w, c), padding, pads
+DWLN_CASES = [((2, 9, 11, 96), "SAME", (0, 0, 0, 0)), ((3, 4, 4, 40), "SAME", (0, 0, 0, 0)),
+              ((3, 2, 2, 8), "SAME", (0, 0, 0, 0)), ((2, 9, 8, 24), "VALID", (0, 0, 0, 0)),
+              ((2, 5, 6, 16), "EXPLICIT", (2, 4, 5, 0)), ((2, 5, 6, 16), "EXPLICIT", (0, 7, 2, 1))]
+
+
+def dwln_case_id(case):
+    return "x".join(map(str, case[0])) + "-" + case[1].lower() + ("".join(map(str, case[2])) if any(case[2]) else "")
+
+
+def dwln_padding_only_tail(case):
+    (n, h, w, c), padding, pads = case
+    return dw_padding_only_tail(((7, 7), (n, h, w, c), (1, 1), padding, pads))
+
+
+def dwln_case_inputs(case, scalar=False):
+    (n, h, w, c), _p, _pads = case
+    x = rnd(n, h, w, c, seed=h + c).to(BF).float()
+    wt = rnd(7, 7, c, scale=1 / 7, seed=h + c + 1)
+    b = rnd(c, scale=0.5, seed=h + c + 2)
+    if scalar:
+        return x, wt, b, torch.tensor([1.25]), torch.tensor([-0.375])
+    return x, wt, b, 1 + rnd(c, scale=0.3, seed=h + c + 3), rnd(c, scale=0.3, seed=h + c + 4)
+
+
+# (batch, (h, w), c)
+PATCH_CASES = [(3, (2, 3), 8), (2, (3, 5), 40), (1, (1, 1), 96)]
+
+
+def patch_case_inputs(case, pos_rank):
+    b, (h, w), c = case
+    x = rnd(b, h, w, c, seed=c).to(BF).float()
+    cls = rnd(1, 1, c, seed=c + 1)
+    pos = rnd(h * w + 1, c, scale=0.5, seed=c + 2)
+    return x, cls, pos if pos_rank == 2 else pos[None]
+
+
+# (windows or images, heads, S, nW, grid): S = 49 and 36 (no multiple of 16), H = 3, one and several images
+WATTN_CASES = [(4, 3, 49, None, None), (6, 3, 49, 3, None), (6, 2, 36, 2, None),
+               (2, 3, 49, None, (14, 21, 7, 0)), (2, 3, 49, 6, (14, 21, 7, 3)), (1, 2, 36, 6, (12, 18, 6, 2)),
+               (3, 2, 16, 4, (8, 8, 4, 1))]
+
+
+def wattn_case_inputs(case, dh=32):
+    n, heads, s, nw, grid = case
+    rows = n * s if grid is None else n * grid[0] * grid[1]
+    return ab.inputs(rows, heads, s, nw, seed=s + heads, dh=dh)
+
+
+# (vocab, hot, d): tables of different V, hotness mixes with 1
+BAG_TABLES = [((5, 9, 3), (2, 1, 3), 16), ((4, 7), (1, 1), 8), ((6, 11, 2, 8), (4, 1, 1, 2), 40)]
+BAG_BATCHES = (1, 3, 65)
+
+
+def bag_case_inputs(vocab, hot, d, b, dtype=torch.int64, lead=False):
+    ids, tables = ib.embag_inputs(b, vocab, hot, d, seed=b + d)
+    dense = rnd(b, d, seed=b + d + 1).to(BF).float() if lead else None
+    return ids.to(dtype), [t.float() for t in tables], dense
+
+
+INTERACT_F, INTERACT_D, INTERACT_DD = (2, 17, 27), (32, 128), 16
+
+
+def interact_pads(f, self_interaction):
+    """0 and the smallest pad > 0 that leaves Dd + P + pad short of the kernel's ceil8 width."""
+    w = INTERACT_DD + len(tril_order(f, self_interaction))
+    return (0, next(p for p in range(1, 9) if (w + p) % 8))
+
+
+def interact_case_inputs(b, f, d, dd=INTERACT_DD):
+    z = rnd(b, f, d, seed=f + d).to(BF)
+    return z, rnd(b, dd, seed=f + d + 1).to(BF)

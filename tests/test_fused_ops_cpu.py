@@ -7,15 +7,23 @@ test_fused_ops_gpu.py tested on the CPU.
      weights the test started from; every padding element is exactly zero.
  (b) The cases can see the bugs they exist for: at the shapes the GPU module
      runs, an ideal fp32 emulation stays inside the bound at every element and
-     each mutant (a subtly wrong op) is rejected."""
+     each mutant (a subtly wrong op) is rejected.
+ (d) The same for the op classes of the later model families (depthwise conv,
+     depthwise + LayerNorm, patch tokens, windowed attention, embedding bag, dot
+     interaction): ideal emulation and the op's CPU path inside the bound, the
+     mutants of the argument arithmetic those classes own rejected."""
+import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
+import dwconv_bounds as db
 import fused_op_refs as fr
+import interact_bounds as ib
 import kernel_bounds as kb
 from kernel_bounds import BF, rnd
 from rust_tensorflow_serving2_amd.graph import fused as FU
+from rust_tensorflow_serving2_amd.graph import patterns as PT
 
 CPU = torch.device("cpu")
 
@@ -334,3 +342,279 @@ def test_window_override_is_the_padded_rgba_filter(k, s):
         assert (ho, wo) == fr.out_hw(h, w, k, k, s, s, p)
         hp, wp = (ho - 1) * s + op.khp, (wo - 1) * s + 8
         assert op.out_hw(hp, wp, (0, 0, 0, 0), op.khp, 8) == (ho, wo) == fr.out_hw(hp, wp, op.khp, 8, s, s, (0,) * 4)
+
+
+# ================================================================== (d) the op classes of the later model families
+def act32(act, v):
+    if act == "relu6":
+        return torch.clamp(v, 0.0, 6.0)
+    if act == "hard_swish":
+        return v * (torch.clamp(v + 3.0, 0.0, 6.0) / 6.0)
+    if act == "swish":
+        return v * torch.sigmoid(v)
+    return kb.act64(act, v)
+
+
+def conv_dw32(x, wt, b, strides, p):
+    kh, kw, c = wt.shape
+    pt, pb, pl, pr = p
+    return F.conv2d(F.pad(x.float().permute(0, 3, 1, 2), [pl, pr, pt, pb]), wt.permute(2, 0, 1).reshape(c, 1, kh, kw),
+                    stride=tuple(strides), groups=c).permute(0, 2, 3, 1) + b
+
+
+@pytest.mark.parametrize("case", fr.DW_CASES, ids=fr.dw_case_id)
+def test_depthwise_cases_ideal_within_bound_and_mutants_rejected(case):
+    (kh, kw), _img, strides, padding, pads = case
+    x, wt, b = fr.dw_case_inputs(case)
+    p = fr.tf_pads(x.shape[1], x.shape[2], kh, kw, strides[0], strides[1], padding, pads)
+    op = FU.FusedDepthwiseConv(wt, b, strides, padding, pads, "none", CPU, False, "dw")
+    assert op.pads_for(x.shape[1], x.shape[2]) == p
+    parts = fr.dw_parts_tf(x, wt, b, strides, padding, pads)
+    for act in fr.DW_ACTS:
+        ref, bound = fr.dw_epilogue(*parts, act)
+        assert tuple(ref.shape[1:3]) == fr.out_hw(x.shape[1], x.shape[2], kh, kw, strides[0], strides[1], p)
+        kb.assert_within(bf_round(act32(act, conv_dw32(x, wt, b, strides, p))), ref, bound, f"ideal {act}")
+        op.act = act
+        kb.assert_within(bf_round(op(None, None, [x])[0]), ref, bound, f"CPU op {act}")
+        if p[0] != p[1] or p[2] != p[3]:
+            rejected(bf_round(act32(act, conv_dw32(x, wt, b, strides, (p[1], p[0], p[3], p[2])))), ref, bound,
+                     "pads on the other side")
+        if kh != kw:
+            swapped = wt.permute(1, 0, 2).reshape(kh, kw, -1)
+            rejected(bf_round(act32(act, conv_dw32(x, swapped, b, strides, p))), ref, bound, "kh / kw swapped")
+
+
+def test_depthwise_cases_reach_what_they_exist_for():
+    """Every filter meets SAME at an even size with stride 2 (pads differ front and back); 3x5 is there;
+    the inputs reach both clamps of relu6 / hard-swish."""
+    uneven = set()
+    for (kh, kw), (n, h, w, c), (sh, sw), padding, pads in fr.DW_CASES:
+        if padding == "SAME" and (sh, sw) == (2, 2) and h % 2 == 0 and w % 2 == 0:
+            p = fr.tf_pads(h, w, kh, kw, sh, sw, padding)
+            assert p[0] + 1 == p[1] and p[2] + 1 == p[3]
+            uneven.add((kh, kw))
+    assert uneven == {(3, 3), (5, 5), (7, 7), (3, 5)}
+    assert {fr.dw_kernel(c) for c in fr.DW_CASES} == {"dwconv", "dwconv5x5", None}
+    tails = [c for c in fr.DW_CASES if fr.dw_padding_only_tail(c)]
+    assert tails and all(c[3] == "EXPLICIT" and c[0] == (3, 3) for c in tails)
+    # each strip kernel and the generic one also meet EXPLICIT pads that differ front and back
+    kernels = {fr.dw_kernel(c) for c in fr.DW_CASES if c[3] == "EXPLICIT" and not fr.dw_padding_only_tail(c)}
+    assert kernels == {"dwconv", "dwconv5x5", None}
+    assert [fr.dwln_padding_only_tail(c) for c in fr.DWLN_CASES].count(True) == 1
+    x, wt, b = fr.dw_case_inputs(fr.DW_CASES[0])
+    pre, _mag = db.dw_parts(x, wt, b, 1, (1, 1, 1, 1))
+    for act in ("none", "relu", "relu6"):               # fr.dw_epilogue's line is dwconv_bounds.dw_ref's
+        for got, want in zip(fr.dw_ref(x, wt, b, (1, 1), "SAME", act=act), db.dw_ref(x, wt, b, 1, (1, 1, 1, 1), act)):
+            assert torch.equal(got, want)
+    assert (pre < -3).any() and (pre > 6).any() and ((pre > -3) & (pre < 3)).any()
+
+
+def ln32(v, gamma, beta, eps):
+    c = v.shape[-1]
+    return F.layer_norm(v, (c,), gamma.reshape(-1).expand(c), beta.reshape(-1).expand(c), eps)
+
+
+@pytest.mark.parametrize("scalar", [False, True])
+@pytest.mark.parametrize("case", fr.DWLN_CASES, ids=fr.dwln_case_id)
+def test_depthwise_layernorm_cases_fused_and_pair(case, scalar):
+    """The fused arithmetic is inside dwln_bounds' bound; the pair (a bf16 conv output in between) is inside
+    the derived pair bound and, wherever the map has more than a handful of elements, OUTSIDE the fused one."""
+    (n, h, w, c), padding, pads = case
+    x, wt, b, gm, bt = fr.dwln_case_inputs(case, scalar)
+    eps = 1e-6
+    p = fr.tf_pads(h, w, 7, 7, 1, 1, padding, pads)
+    v = conv_dw32(x, wt, b, (1, 1), p)
+    ref, bound = fr.dwln_ref(x, wt, b, gm, bt, eps, padding, pads)
+    kb.assert_within(bf_round(ln32(v, gm, bt, eps)), ref, bound, "ideal fused")
+    pair = bf_round(ln32(bf_round(v), gm, bt, eps))
+    ref2, bound2 = fr.dwln_ref(x, wt, b, gm, bt, eps, padding, pads, fused=False)
+    assert torch.equal(ref, ref2) and (bound2 > bound).all()
+    kb.assert_within(pair, ref2, bound2, "ideal pair")
+    if ref.numel() >= 256:
+        rejected(pair, ref, bound, "the pair's bf16 intermediate under the fused bound")
+    dw = FU.FusedDepthwiseConv(wt, b, (1, 1), padding, pads, "none", CPU, False, "dw")
+    op = FU.FusedDepthwiseLN(dw, PT.LayerNormOp(gm, bt, eps, CPU, False), False, "dwln")
+    assert FU.FusedDepthwiseLN.shape_ok(dw)
+    kb.assert_within(bf_round(op(None, None, [x])[0]), ref, bound, "CPU op")
+    if padding == "SAME":
+        assert p == (3, 3, 3, 3)
+    if p[0] != p[1]:
+        rejected(bf_round(ln32(conv_dw32(x, wt, b, (1, 1), (p[1], p[0], p[3], p[2])), gm, bt, eps)), ref, bound,
+                 "pads on the other side")
+
+
+@pytest.mark.parametrize("pos_rank", [2, 3])
+@pytest.mark.parametrize("case", fr.PATCH_CASES, ids=str)
+def test_patch_tokens_cases_ideal_within_bound_and_mutants_rejected(case, pos_rank):
+    batch, (h, w), c = case
+    x, cls, pos = fr.patch_case_inputs(case, pos_rank)
+    ref, bound = fr.patch_tokens_ref(x, cls, pos, batch)
+    assert tuple(ref.shape) == (batch, h * w + 1, c)
+    table = pos.reshape(-1, c).clone()
+
+    def ideal(t):
+        return bf_round(torch.cat([t[0].expand(batch, 1, c), x.reshape(batch, -1, c) + t[1:]], 1))
+    right = table.clone()
+    right[0] += cls.reshape(c)
+    kb.assert_within(ideal(right), ref, bound, "ideal")
+    rejected(ideal(table + cls.reshape(c)), ref, bound, "the class token added to every row")
+    only_cls = table.clone()
+    only_cls[0] = cls.reshape(c)
+    rejected(ideal(only_cls), ref, bound, "pos[0] dropped from row 0")
+    op = FU.PatchTokens(cls, pos, h * w, c, CPU, False, "pt")
+    kb.assert_within(bf_round(op(None, None, [x, torch.tensor(batch)])[0]), ref, bound, "CPU op")
+    # what the GPU branch reads: row 0 is the one fp32 sum, the rest is pos as given
+    hip_op = FU.PatchTokens(cls, pos, h * w, c, CPU, True, "pt")
+    assert fr.same_bits(hip_op.table, right) and hip_op.pos_rank == pos_rank
+
+
+def ideal_wattn(qkv, bias, mask, heads, scale, grid=None, roll_sign=-1, mask_div=False, roll_back=True):
+    """Windowed attention in fp32 with one bf16 store.  The mutants: the cyclic shift in the other
+    direction, the mask window as bw // (Bw / nW), no roll on the way back."""
+    s = bias.shape[1]
+    rows, w3 = qkv.shape
+    t = qkv.float()
+    if grid is not None:
+        hf, wf, ws, shift = grid
+        b = rows // (hf * wf)
+        t = torch.roll(t.reshape(b, hf, wf, w3), (roll_sign * shift, roll_sign * shift), (1, 2))
+        t = t.reshape(b, hf // ws, ws, wf // ws, ws, w3).transpose(2, 3).reshape(rows, w3)
+    bw = rows // s
+    q, k, v = t.reshape(bw, s, 3, heads, -1).permute(2, 0, 3, 1, 4)
+    sc = q @ k.transpose(-1, -2) * scale + bias[None]
+    if mask is not None:
+        nw = mask.shape[0]
+        idx = torch.arange(bw) // (bw // nw) if mask_div else torch.arange(bw) % nw
+        sc = sc + mask[idx][:, None]
+    y = (torch.softmax(sc, -1) @ v).permute(0, 2, 1, 3).reshape(rows, -1)
+    if grid is not None:
+        y = y.reshape(b, hf // ws, wf // ws, ws, ws, -1).transpose(2, 3).reshape(b, hf, wf, -1)
+        if roll_back:
+            y = torch.roll(y, (-roll_sign * shift, -roll_sign * shift), (1, 2))
+        y = y.reshape(rows, -1)
+    return bf_round(y)
+
+
+@pytest.mark.parametrize("case", fr.WATTN_CASES, ids=str)
+def test_window_attention_cases_ideal_within_bound_and_mutants_rejected(case):
+    n, heads, s, nw, grid = case
+    qkv, bias, mask = fr.wattn_case_inputs(case)
+    scale = 32 ** -0.5
+    ref, bound = fr.wattn_ref(qkv, bias, mask, heads, scale, grid)
+    kb.assert_within(ideal_wattn(qkv, bias, mask, heads, scale, grid), ref, bound, "ideal")
+    op = PT.WindowAttentionOp(heads, 32, s, scale, bias, mask, CPU, False)
+    op.grid = grid
+    kb.assert_within(bf_round(op(None, None, [qkv])[0]), ref, bound, "CPU op")
+    if grid is not None and grid[3]:
+        rejected(ideal_wattn(qkv, bias, mask, heads, scale, grid, roll_sign=1), ref, bound, "shift with the wrong sign")
+        rejected(ideal_wattn(qkv, bias, mask, heads, scale, grid, roll_back=False), ref, bound, "reverse roll omitted")
+    if nw is not None and qkv.shape[0] // s > nw:
+        rejected(ideal_wattn(qkv, bias, mask, heads, scale, grid, mask_div=True), ref, bound,
+                 "mask window bw // (Bw / nW)")
+
+
+def test_window_attention_cases_reach_what_they_exist_for():
+    shifts = {c[4][3] for c in fr.WATTN_CASES if c[4] is not None}
+    assert 0 in shifts and max(shifts) > 0
+    assert any(c[4] is None and c[3] is None for c in fr.WATTN_CASES)
+    assert any(c[4] is None and c[3] and c[0] > c[3] for c in fr.WATTN_CASES)
+    assert any(c[4] is not None and c[3] and c[0] > 1 for c in fr.WATTN_CASES)      # several images share nW masks
+    assert {49} < {c[2] for c in fr.WATTN_CASES} and any(c[2] % 16 for c in fr.WATTN_CASES if c[2] != 49)
+
+
+def bag_table(vocab, hot):
+    """(row base, V, first slot, hotness) per feature, from running sums written out here."""
+    out, base, first = [], 0, 0
+    for v, l in zip(vocab, hot):
+        out.append([base, v, first, l])
+        base, first = base + v, first + l
+    return out
+
+
+def bag_from_table(ids, blob, feat, dense=None, dense_last=False):
+    """The kernel's arithmetic over a feature table: fp32 adds in slot order, one rounding."""
+    outs = []
+    for base, v, first, l in feat:
+        idx = ids[:, first:first + l].long()
+        assert idx.shape[1] == l
+        ok = (idx >= 0) & (idx < v)
+        rows = torch.where(ok[..., None], blob[idx.clamp(0, v - 1) + base], torch.zeros(()))
+        acc = rows[:, 0]
+        for s in range(1, l):
+            acc = acc + rows[:, s]
+        outs.append(bf_round(acc))
+    if dense is not None:
+        outs = outs + [dense] if dense_last else [dense] + outs
+    return torch.stack(outs, 1)
+
+
+@pytest.mark.parametrize("b", fr.BAG_BATCHES)
+@pytest.mark.parametrize("lead", [False, True])
+@pytest.mark.parametrize("vocab,hot,d", fr.BAG_TABLES, ids=str)
+def test_embedding_bag_cases_ideal_within_bound_and_mutants_rejected(vocab, hot, d, lead, b):
+    ids, tables, dense = fr.bag_case_inputs(vocab, hot, d, b, lead=lead)
+    ref, bound = fr.bag_ref(ids, tables, hot, dense)
+    assert tuple(ref.shape) == (b, len(vocab) + lead, d)
+    blob = torch.cat(tables, 0)
+    feat = bag_table(vocab, hot)
+    kb.assert_within(bag_from_table(ids, blob, feat, dense), ref, bound, "ideal")
+    # the table the op builds for the kernel is this one
+    hip_op = PT.EmbeddingBagOp(tables, list(hot), lead, False, CPU, True, "bag")
+    assert hip_op.features(list(hot), CPU)[0] == [v for row in feat for v in row]
+    assert fr.same_bits(hip_op.blob, blob.to(BF))
+    # the op's CPU path, in the split form and from a list of id tensors, concat or stack, int32 or int64
+    for split, concat, dt in ((True, False, torch.int64), (False, True, torch.int32), (True, True, torch.int32),
+                              (False, False, torch.int64)):
+        op = PT.EmbeddingBagOp(tables, list(hot) if split else None, lead, concat, CPU, False, "bag")
+        id_ins = [ids.to(dt)] if split else list(torch.split(ids.to(dt), list(hot), 1))
+        y = op(None, None, ([dense] if lead else []) + id_ins)[0]
+        kb.assert_within(bf_round(y), ref, bound, f"CPU op split={split} concat={concat} {dt}")
+    # mutants of the table
+    firsts, wrong = [r[2] for r in feat], []
+    first = 0
+    for f, l in enumerate(hot):
+        wrong.append(min(first, sum(hot) - l))
+        first += hot[(f + 1) % len(hot)]                    # the next feature's hotness, not this one's
+    if wrong != firsts and b > 1:
+        bad = [[r[0], r[1], w, r[3]] for r, w in zip(feat, wrong)]
+        rejected(bag_from_table(ids, blob, bad, dense), ref, bound, "first slot from the wrong feature's hotness")
+    if b > 1:
+        bad = [[feat[1][0]] + feat[0][1:], [feat[0][0]] + feat[1][1:]] + feat[2:]
+        assert all(r[0] + r[1] <= blob.shape[0] for r in bad)
+        rejected(bag_from_table(ids, blob, bad, dense), ref, bound, "row bases of two tables exchanged")
+    if lead:
+        rejected(bag_from_table(ids, blob, feat, dense, dense_last=True), ref, bound, "the dense row placed last")
+
+
+def test_embedding_bag_cases_reach_what_they_exist_for():
+    assert all(len(set(v)) > 1 for v, _h, _d in fr.BAG_TABLES)                        # tables of different V
+    assert all(1 in h for _v, h, _d in fr.BAG_TABLES) and any(max(h) > 1 for _v, h, _d in fr.BAG_TABLES)
+    assert sum(len(set(h)) > 1 for _v, h, _d in fr.BAG_TABLES) >= 2                   # the first-slot mutant can show
+
+
+@pytest.mark.parametrize("self_interaction", [False, True])
+@pytest.mark.parametrize("d", fr.INTERACT_D)
+@pytest.mark.parametrize("f", fr.INTERACT_F)
+def test_dot_interaction_cases_ideal_within_bound_and_mutants_rejected(f, d, self_interaction):
+    k = 0 if self_interaction else -1
+    ii, jj = np.tril_indices(f, k)
+    assert fr.tril_order(f, self_interaction) == list(zip(ii.tolist(), jj.tolist()))
+    assert PT.tril_pairs(f, k) == [i * f + j for i, j in fr.tril_order(f, self_interaction)]
+    z, dense = fr.interact_case_inputs(3, f, d)
+    pads = fr.interact_pads(f, self_interaction)
+    assert pads[0] == 0 and ib.width(f, dense.shape[1], pads[1], k) > dense.shape[1] + len(ii) + pads[1]
+    for pad in pads:
+        ref, bound = fr.interact_ref(z, dense, self_interaction, pad)
+        w = dense.shape[1] + len(ii) + pad
+        assert ref.shape[1] == w
+        kb.assert_within(ib.interact_emulate(z, dense, k, pad)[:, :w], ref, bound, "ideal")
+        op = PT.DotInteractionOp(f, self_interaction, pad, CPU, False, "dot")
+        kb.assert_within(bf_round(op(None, None, [z.float(), dense.float()])[0]), ref, bound, "CPU op")
+        if f > 3:
+            rejected(ib.interact_emulate(z, dense, k, pad, upper=True)[:, :w], ref, bound, "upper-triangle pair order")
+        other = ib.interact_emulate(z, dense, -1 - k, f + 8)[:, :w]
+        rejected(other, ref, bound, "self-interaction on where it is off (or off where it is on)")
+        if pad:
+            y = ib.interact_emulate(z, dense, k, pad)[:, :w].clone()
+            y[:, -1] = 2.0 ** -20
+            rejected(y, ref, bound, "a non-zero pad tail")

@@ -13,15 +13,26 @@ the dispatch and the pick:
  (d) three tiny graphs through the fusion passes: folded weights elementwise,
      then the output.
 
+The second half does (a) to (d) for the op classes of the later model families
+(depthwise conv, depthwise + LayerNorm, patch tokens, windowed attention,
+embedding bag, dot interaction, the attention forms): their choices go through
+ops.tuned_choice, and which kernel ran is also read from a count of the
+bindings called; its graphs are the small builders of the fusion test modules.
+
 ops.tuned_config / ops.tuned_choice are replaced by the `picks` fixture (the op
 classes import them inside __call__), so no timing loop runs and neither the
 committed nor a remote pick table is read.
 
-Set FUSED_OPS_REPORT=<path> for the worst err / bound per op class and the
-candidates each case rejected, as JSON (the table in docs/numerics.md)."""
+Set FUSED_OPS_REPORT=<path> for the worst err / bound per op class, the
+candidates each case rejected and the module's run time, as JSON (the tables in
+docs/numerics.md)."""
+import collections
 import json
 import math
 import os
+import time
+
+import numpy as np
 
 import pytest
 import torch
@@ -44,6 +55,13 @@ WORST = {}
 REJECTED = {}
 REAL_TUNED_CONFIG = ops.tuned_config
 REAL_TUNED_CHOICE = ops.tuned_choice
+CLOCK = {}
+
+
+@pytest.fixture(scope="module", autouse=True)
+def module_clock():
+    """When this module's first test started (the report's run time; no test reads it)."""
+    CLOCK["t0"] = time.perf_counter()
 
 
 def within(family, y, ref, bound, what):
@@ -924,11 +942,507 @@ def test_graph_projecting_block_becomes_a_dual_conv(picks):
     within("graph projecting block", yv, ref, bound, "output")
 
 
+# ================================================================== the op classes of the later model families
+# FusedDepthwiseConv, FusedDepthwiseLN, PatchTokens, WindowAttentionOp, EmbeddingBagOp, DotInteractionOp and
+# the AttentionOp forms: (a) every dispatch branch, (b) every option of every tuned_choice, (c) the keys.
+# Which branch ran is read from picks.choices and from `launches`, a count of the kernel bindings called.
+NEW_KERNELS = ("dwconv2d", "dwconv_ln", "layernorm", "patch_tokens", "window_attention", "embedding_bag",
+               "dot_interaction", "attention")
+
+
+@pytest.fixture
+def launches(monkeypatch):
+    count = collections.Counter()
+
+    def counted(name, real):
+        def call(*a, **k):
+            count[name] += 1
+            return real(*a, **k)
+        return call
+    for name in NEW_KERNELS:
+        monkeypatch.setattr(hip(), name, counted(name, getattr(hip(), name)))
+    return count
+
+
+def choices_since(picks, n0, key0=None):
+    new = picks.choices[n0:]
+    assert all(c["offered"] == c["default"] for c in new), "an untuned choice is the default"
+    if key0 is None:
+        assert not new, f"no tuned_choice expected, got {[c['key'] for c in new]}"
+        return None
+    assert len(new) == 1 and new[0]["key"][0] == key0, [c["key"] for c in new]
+    return new[0]
+
+
+DW_OPTIONS = {"dwconv": [2, 8], "dwconv5x5": [0, 2, 4], None: []}
+
+
+@pytest.mark.parametrize("case", fr.DW_CASES, ids=fr.dw_case_id)
+def test_depthwise_op_every_branch_and_option_within_bound(picks, launches, case):
+    """(a) and (b) in one pass over the fp64 reference: the untuned pick, then every strip / 5x5 form the
+    tuner would time, all five activations; a bf16 input and the same values as fp32 on the device."""
+    (kh, kw), (n, h, w, c), strides, padding, pads = case
+    x, wt, b = fr.dw_case_inputs(case)
+    parts = fr.dw_parts_tf(x, wt, b, strides, padding, pads)
+    assert FU.FusedDepthwiseConv.hip_ok(kh, kw, c)
+    op = FU.FusedDepthwiseConv(wt, b, strides, padding, pads, "none", DEV, True, "dw")
+    kern = fr.dw_kernel(case)
+    fam = "FusedDepthwiseConv " + (kern or "generic")
+    xb, xf = dev(x.to(BF)), dev(x)
+    if fr.dw_padding_only_tail(case):
+        # the last window holds bottom / right padding alone: dwconv2d does not take it, torch on the device
+        for act in fr.DW_ACTS:
+            op.act = act
+            for xin in (xb, xf):
+                y = op(None, None, [xin])[0]
+                assert y.dtype == BF and not launches and not picks.choices
+                within("FusedDepthwiseConv fallback", y, *fr.dw_epilogue(*parts, act), f"{fr.dw_case_id(case)} {act}")
+        return
+    forms = [int(f) for f in hip().dwconv_forms(n, parts[0].shape[1], parts[0].shape[2], c, kh, kw, *strides)]
+    assert forms == ([0] + DW_OPTIONS[kern] if kern != "dwconv5x5" else DW_OPTIONS[kern])
+    for act in fr.DW_ACTS:
+        op.act = act
+        ref, bound = fr.dw_epilogue(*parts, act)
+        n0 = len(picks.choices)
+        y = op(None, None, [xb])[0]
+        ch = choices_since(picks, n0, kern)
+        assert y.dtype == BF and tuple(y.shape) == tuple(ref.shape) and launches["dwconv2d"] == 1
+        within(fam, y, ref, bound, f"{fr.dw_case_id(case)} {act} untuned")
+        assert torch.equal(op(None, None, [xf])[0], y), "fp32 on the device: cast, then the same launch"
+        outs = {}
+        if ch is not None:
+            assert ch["options"] == DW_OPTIONS[kern] and ch["key"][-1] == act and ch["key"][1] == tuple(x.shape)
+            for o in ch["options"]:
+                picks.choice = o
+                outs[o] = op(None, None, [xb])[0]
+                within(fam + " options", outs[o], ref, bound, f"{fr.dw_case_id(case)} {act} option {o}")
+            picks.choice = None
+            assert any(torch.equal(v, y) for v in outs.values())
+            if kern == "dwconv5x5":
+                assert torch.equal(outs[0], outs[2]) and torch.equal(outs[0], outs[4]), "the 5x5 forms are bit-equal"
+        assert launches["dwconv2d"] == 2 + len(outs)
+        launches.clear()
+
+
+def test_depthwise_keys_that_must_not_be_shared(picks):
+    """Two ops that differ in one thing only never record the same key (an op on the one-form generic
+    kernel records none: nothing of a strip kernel's can reach it)."""
+    def key_of(k, img, s, act="relu6", padding="SAME"):
+        case = (k, img, s, padding, (0, 0, 0, 0))
+        x, wt, b = fr.dw_case_inputs(case)
+        n0 = len(picks.choices)
+        FU.FusedDepthwiseConv(wt, b, s, padding, (0, 0, 0, 0), act, DEV, True, "dw")(None, None, [dev(x.to(BF))])
+        new = picks.choices[n0:]
+        assert len(new) == (fr.dw_kernel(case) is not None)
+        return new[0]["key"] if new else None
+    img = (2, 12, 14, 16)
+    for k in ((3, 3), (5, 5)):
+        base = key_of(k, img, (1, 1))
+        assert base is not None and key_of(k, img, (1, 2)) is None                      # sw
+        assert key_of(k, img, (2, 2)) != base
+        assert key_of(k, img, (1, 1), act="relu") != base                               # the activation
+        # SAME at stride 2: an even size pads (0, 1), an odd one (1, 1); the output is 6 x 7 for both
+        even, odd = key_of(k, img, (2, 2)), key_of(k, (2, 11, 13, 16), (2, 2))
+        assert even != odd and even[-3:-1] == odd[-3:-1] == (6, 7)
+        pads = even[-5:-3], odd[-5:-3]
+        assert pads == (((k[0] - 2) // 2, (k[1] - 2) // 2), ((k[0] - 1) // 2, (k[1] - 1) // 2))
+    k3, k5 = key_of((3, 3), img, (1, 1)), key_of((5, 5), img, (1, 1))                      # 3x3 against 5x5
+    assert k3[0] == "dwconv" and k5[0] == "dwconv5x5" and k3[1] == k5[1] and k3 != k5
+
+
+@pytest.mark.parametrize("scalar", [False, True])
+@pytest.mark.parametrize("case", fr.DWLN_CASES, ids=fr.dwln_case_id)
+def test_depthwise_layernorm_op_kernel_and_pair_within_bound(picks, launches, monkeypatch, case, scalar):
+    (n, h, w, c), padding, pads = case
+    x, wt, b, gm, bt = fr.dwln_case_inputs(case, scalar)
+    eps = 1e-6
+    dw = FU.FusedDepthwiseConv(wt, b, (1, 1), padding, pads, "none", DEV, True, "dw")
+    ln = PT.LayerNormOp(gm, bt, eps, DEV, True)
+    op = FU.FusedDepthwiseLN(dw, ln, True, "dwln")
+    assert FU.FusedDepthwiseLN.shape_ok(dw) and hip().dwconv_ln_supported(1, 1, 1, c, 7, 7, 1, 1)
+    tail = fr.dwln_padding_only_tail(case)       # the kernel does not take it: the pair, its conv with torch
+    ref, bound = fr.dwln_ref(x, wt, b, gm, bt, eps, padding, pads, fused=not tail)
+    for xin in (dev(x.to(BF)), dev(x)):
+        y = op(None, None, [xin])[0]
+        assert y.dtype == BF and tuple(y.shape) == tuple(ref.shape)
+        within("FusedDepthwiseLN" + (" pair" if tail else ""), y, ref, bound, f"{case} scalar={scalar} {xin.dtype}")
+    assert dict(launches) == ({"layernorm": 2} if tail else {"dwconv_ln": 2})
+    if scalar:
+        rows = ln._rows
+        assert rows is not None and rows[0] == c and rows[1].numel() == c
+        op(None, None, [dev(x.to(BF))])
+        assert ln._rows is rows, "the expanded gamma / beta rows are cached"
+    launches.clear()
+    monkeypatch.setenv("TFSERVE_DWLN", "0")
+    ref, bound = fr.dwln_ref(x, wt, b, gm, bt, eps, padding, pads, fused=False)
+    y = op(None, None, [dev(x.to(BF))])[0]
+    assert dict(launches) == ({"layernorm": 1} if tail else {"dwconv2d": 1, "layernorm": 1}) and not picks.choices
+    assert y.dtype == BF and tuple(y.shape) == tuple(ref.shape)
+    within("FusedDepthwiseLN pair", y, ref, bound, f"{case} scalar={scalar} TFSERVE_DWLN=0")
+
+
+def test_depthwise_layernorm_op_pair_for_what_the_kernel_refuses(picks, launches):
+    """More channels than kernels/dwln.hip takes, and an input of another depth (the pair's own error, not
+    the fused kernel's, is the op's answer): both run dwconv2d + layernorm, under the pair bound."""
+    case = ((1, 4, 4, 1032), "SAME", (0, 0, 0, 0))
+    x, wt, b, gm, bt = fr.dwln_case_inputs(case)
+    assert not hip().dwconv_ln_supported(1, 4, 4, 1032, 7, 7, 1, 1)
+    dw = FU.FusedDepthwiseConv(wt, b, (1, 1), "SAME", (0, 0, 0, 0), "none", DEV, True, "dw")
+    op = FU.FusedDepthwiseLN(dw, PT.LayerNormOp(gm, bt, 1e-6, DEV, True), True, "dwln")
+    ref, bound = fr.dwln_ref(x, wt, b, gm, bt, 1e-6, "SAME", fused=False)
+    y = op(None, None, [dev(x.to(BF))])[0]
+    assert dict(launches) == {"dwconv2d": 1, "layernorm": 1} and y.dtype == BF
+    within("FusedDepthwiseLN pair", y, ref, bound, "C = 1032")
+    # an input of another depth goes to the pair as it is, and dwconv2d refuses it before any launch (the
+    # filter has C channels): the fused kernel never sees it
+    launches.clear()
+    dw8 = FU.FusedDepthwiseConv(wt[:, :, :16], b[:16], (1, 1), "SAME", (0, 0, 0, 0), "none", DEV, True, "dw")
+    op8 = FU.FusedDepthwiseLN(dw8, PT.LayerNormOp(gm[:16], bt[:16], 1e-6, DEV, True), True, "dwln")
+    with pytest.raises(RuntimeError):
+        op8(None, None, [dev(x.to(BF))[..., :24].contiguous()])
+    assert dict(launches) == {"dwconv2d": 1}, "refused by the depthwise binding: nothing after it ran"
+
+
+@pytest.mark.parametrize("pos_rank", [2, 3])
+@pytest.mark.parametrize("case", fr.PATCH_CASES, ids=str)
+def test_patch_tokens_op_branches_within_bound(picks, launches, case, pos_rank):
+    b, (h, w), c = case
+    x, cls, pos = fr.patch_case_inputs(case, pos_rank)
+    ref, bound = fr.patch_tokens_ref(x, cls, pos, b)
+    op = FU.PatchTokens(cls, pos, h * w, c, DEV, True, "pt")
+    assert hip().patch_tokens_supported(b, h * w, c)
+    bt = torch.tensor(b)
+    for xin in (dev(x.to(BF)), dev(x)):
+        y = op(None, None, [xin, bt])[0]
+        assert y.dtype == BF and tuple(y.shape) == (b, h * w + 1, c)
+        within("PatchTokens", y, ref, bound, f"{case} pos rank {pos_rank} {xin.dtype}")
+    assert dict(launches) == {"patch_tokens": 2}
+    # torch on the device: a rank-3 x, and a rank-4 x whose leading extent is not the batch
+    others = [dev(x.to(BF)).reshape(b, h * w, c), dev(x).reshape(b, h * w, c)]
+    if (h * w) % 2 == 0:
+        others.append(dev(x.to(BF)).reshape(2 * b, 1, h * w // 2, c))
+    for xin in others:
+        y = op(None, None, [xin, bt])[0]
+        assert y.dtype == xin.dtype and tuple(y.shape) == (b, h * w + 1, c)
+        within("PatchTokens fallback", y, ref, bound, f"{case} pos rank {pos_rank} x {tuple(xin.shape)} {xin.dtype}")
+    assert dict(launches) == {"patch_tokens": 2}
+
+
+def test_patch_tokens_op_torch_branch_for_a_refused_shape(picks, launches):
+    case = (2, (2, 3), 12)                                        # C % 8 != 0
+    x, cls, pos = fr.patch_case_inputs(case, 3)
+    assert not hip().patch_tokens_supported(2, 6, 12)
+    ref, bound = fr.patch_tokens_ref(x, cls, pos, 2)
+    y = FU.PatchTokens(cls, pos, 6, 12, DEV, True, "pt")(None, None, [dev(x.to(BF)), torch.tensor(2)])[0]
+    assert y.dtype == BF and not launches
+    within("PatchTokens fallback", y, ref, bound, "C = 12")
+
+
+@pytest.mark.parametrize("case", fr.WATTN_CASES, ids=str)
+def test_window_attention_op_kernel_and_torch_within_bound(picks, launches, monkeypatch, case):
+    n, heads, s, nw, grid = case
+    qkv, bias, mask = fr.wattn_case_inputs(case)
+    scale = 32 ** -0.5
+    ref, bound = fr.wattn_ref(qkv, bias, mask, heads, scale, grid)
+    op = PT.WindowAttentionOp(heads, 32, s, scale, bias, mask, DEV, True)
+    op.grid = grid
+    assert op.nw == (nw or 0) and op.kernel_ok(dev(qkv))
+    for tag in ("", " fallback"):
+        y = op(None, None, [dev(qkv)])[0]
+        assert y.dtype == BF and tuple(y.shape) == (qkv.shape[0], heads * 32)
+        within("WindowAttentionOp" + tag, y, ref, bound, f"{case}{tag}")
+        assert dict(launches) == {"window_attention": 1} and not picks.choices
+        monkeypatch.setenv("TFSERVE_WATTN", "0")
+
+
+@pytest.mark.parametrize("case,dh", [((4, 2, 36, 2, None), 16), ((1, 3, 16, 4, (8, 8, 4, 1)), 64),
+                                     ((2, 2, 81, 2, None), 32), ((1, 2, 81, 4, (18, 18, 9, 4)), 32)])
+def test_window_attention_op_torch_branch_for_what_the_kernel_refuses(picks, launches, case, dh):
+    """D != 32 and S > 64."""
+    n, heads, s, nw, grid = case
+    qkv, bias, mask = fr.wattn_case_inputs(case, dh)
+    ref, bound = fr.wattn_ref(qkv, bias, mask, heads, dh ** -0.5, grid)
+    op = PT.WindowAttentionOp(heads, dh, s, dh ** -0.5, bias, mask, DEV, True)
+    op.grid = grid
+    y = op(None, None, [dev(qkv)])[0]
+    assert y.dtype == BF and not launches
+    within("WindowAttentionOp fallback", y, ref, bound, f"{case} D={dh}")
+
+
+def bag_ops(tables, hot, lead):
+    """Every (split, concat, ids dtype) form of one bag: (op, the id inputs it takes from ids [B, T])."""
+    for split in (True, False):
+        for concat in (False, True):
+            op = PT.EmbeddingBagOp(tables, list(hot) if split else None, lead, concat, DEV, True, "bag")
+            for dt in (torch.int32, torch.int64):
+                yield (op, (lambda ids, dt=dt, split=split: [dev(ids.to(dt))] if split else
+                            [dev(i.contiguous()) for i in torch.split(ids.to(dt), list(hot), 1)]),
+                       f"split={split} concat={concat} {dt}")
+
+
+@pytest.mark.parametrize("lead", [False, True])
+@pytest.mark.parametrize("vocab,hot,d", fr.BAG_TABLES, ids=str)
+def test_embedding_bag_op_every_form_within_bound(picks, launches, vocab, hot, d, lead):
+    cases = {b: fr.bag_case_inputs(vocab, hot, d, b, lead=lead) for b in fr.BAG_BATCHES}
+    tables = cases[3][1]                                          # one set of tables, ids of every batch size
+    refs = {b: fr.bag_ref(ids, tables, hot, dense) for b, (ids, _t, dense) in cases.items()}
+    # an id outside its table (V_f, -1, far out) adds a zero row: on the kernel branch and on the torch one
+    ids3, _t, dense3 = cases[3]
+    bad = ids3.clone()
+    bad[0, 0], bad[1, hot[0]], bad[2, -1] = vocab[0], -1, 2 ** 31 - 1
+    ref_bad = fr.bag_ref(bad, tables, hot, dense3)
+    assert not torch.equal(ref_bad[0], refs[3][0])
+    for op, id_ins, tag in bag_ops(tables, hot, lead):
+        assert op.blob.dtype == BF and fr.same_bits(op.blob.cpu(), torch.cat(tables, 0).to(BF))
+        for b, (ids, _t, dense) in cases.items():
+            y = op(None, None, ([dev(dense)] if lead else []) + id_ins(ids))[0]
+            assert y.dtype == BF and tuple(y.shape) == (b, len(vocab) + lead, d)
+            within("EmbeddingBagOp", y, *refs[b], f"{vocab} {hot} B={b} lead={lead} {tag}")
+        y = op(None, None, ([dev(dense3.to(BF))] if lead else []) + id_ins(bad))[0]
+        within("EmbeddingBagOp", y, *ref_bad, f"{vocab} {hot} out-of-range ids {tag}")
+        assert dict(launches) == {"embedding_bag": len(cases) + 1}
+        launches.clear()
+    # mixed id dtypes in the list form: torch on the device, the same bound, the same zero rows
+    op = PT.EmbeddingBagOp(tables, None, lead, False, DEV, True, "bag")
+    for ids, ref in ((ids3, refs[3]), (bad, ref_bad)):
+        parts = [dev(i.to(torch.int32 if f % 2 else torch.int64)) for f, i in enumerate(torch.split(ids, list(hot), 1))]
+        y = op(None, None, ([dev(dense3)] if lead else []) + parts)[0]
+        assert y.dtype == BF and tuple(y.shape) == tuple(ref[0].shape) and not launches
+        within("EmbeddingBagOp fallback", y, *ref, f"{vocab} {hot} mixed id dtypes")
+
+
+@pytest.mark.parametrize("self_interaction", [False, True])
+@pytest.mark.parametrize("d", fr.INTERACT_D)
+@pytest.mark.parametrize("f", fr.INTERACT_F)
+def test_dot_interaction_op_kernel_and_torch_within_bound(picks, launches, f, d, self_interaction):
+    H = hip()
+    dd = fr.INTERACT_DD
+    p = len(fr.tril_order(f, self_interaction))
+    for pad in fr.interact_pads(f, self_interaction):
+        op = PT.DotInteractionOp(f, self_interaction, pad, DEV, True, "dot")
+        w = dd + p + pad
+        wp = int(H.dot_interaction_width(f, dd, pad, self_interaction))
+        assert wp >= w and (wp > w if pad else True)
+        for b in (1, 65):
+            z, dense = fr.interact_case_inputs(b, f, d)
+            assert H.dot_interaction_supported(b, f, d, dd, pad, self_interaction)
+            ref, bound = fr.interact_ref(z, dense, self_interaction, pad)
+            y = op(None, None, [dev(z), dev(dense)])[0]
+            assert y.dtype == BF and tuple(y.shape) == (b, w) and y.stride(0) == wp, "the y[:, :w] view of the kernel's rows"
+            within("DotInteractionOp", y, ref, bound, f"F={f} D={d} self={self_interaction} pad={pad} B={b}")
+            assert torch.equal(op(None, None, [dev(z.float()), dev(dense.float())])[0], y)      # fp32 z: cast first
+        assert launches["dot_interaction"] == 4
+        launches.clear()
+        # fewer than 8 dense columns: torch on the device
+        z, dense = fr.interact_case_inputs(3, f, d, dd=4)
+        ref, bound = fr.interact_ref(z, dense, self_interaction, pad)
+        y = op(None, None, [dev(z), dev(dense)])[0]
+        assert y.dtype == BF and tuple(y.shape) == (3, 4 + p + pad) and not launches
+        within("DotInteractionOp fallback", y, ref, bound, f"F={f} D={d} self={self_interaction} pad={pad} Dd=4")
+
+
+@pytest.mark.parametrize("s", [33, 50])
+def test_attention_op_every_form_within_bound(picks, launches, s):
+    """Both kernels of a length that has two (kernels/attention.hip), each forced through the choice,
+    with a key mask; and the key carries the mask layout."""
+    b, h, d = 2, 3, 64
+    qkv = rnd(b, s, 3 * h * d, seed=21 + s).to(BF)
+    keep = torch.ones(b, 1, s, dtype=torch.int32)
+    keep[b - 1, 0, s // 2 + 1:] = 0
+    adder = PT.KeyMaskAdderOp(1.0, -10000.0)(None, None, [dev(keep)])[0]
+    ref, bound = kb.attention_ref(qkv, h, 1 / math.sqrt(d), (1.0 - keep[:, 0].double()) * -10000.0)
+    op = PT.AttentionOp(h, d, s, 1 / math.sqrt(d), True)
+    forms = [int(f) for f in hip().attention_forms(s)]
+    assert forms == [0, 1]
+    outs = []
+    for form in [None] + forms:
+        picks.choice = form
+        y = op(None, None, [dev(qkv).reshape(b * s, 3 * h * d), adder])[0]
+        ch = picks.choices[-1]
+        assert ch["key"] == ("attn", b, s, h, "key") and ch["options"] == forms and ch["offered"] == ch["default"] == 0
+        assert y.dtype == BF and tuple(y.shape) == (b * s, h * d)
+        within("AttentionOp forms", y.reshape(b, s, h * d), ref, bound, f"S={s} form {form}")
+        outs.append(y)
+    assert torch.equal(outs[0], outs[1]) and launches["attention"] == 3
+    # two layouts at the same (B, S, H) do not share a key: a [B, 1, S, S] adder, and none
+    picks.choice = None
+    full = adder.expand(b, 1, s, s).contiguous()
+    y = op(None, None, [dev(qkv), full])[0]
+    assert picks.choices[-1]["key"] == ("attn", b, s, h, "query")
+    within("AttentionOp forms", y.reshape(b, s, h * d), ref, bound, f"S={s} query-layout adder")
+    op(None, None, [dev(qkv)])
+    assert picks.choices[-1]["key"] == ("attn", b, s, h, "none")
+    assert len({c["key"] for c in picks.choices}) == 3
+
+
+# ================================================================== (d) one pattern, one op, through the passes
+# The small graphs of the fusion test modules, compiled with default_passes() on the device: the histogram,
+# the folded parameters against the graph's own constants, then the output under the op's bound.  The
+# inputs are the test's (bf16-valued, in the builders' shapes), the constants are read back from the graph.
+def _compiled(g, feeds, fetch="out"):
+    from rust_tensorflow_serving2_amd.graph.compiler import compile_program
+    from rust_tensorflow_serving2_amd.graph.ir import from_graph_def
+    ir = from_graph_def(g.graph)
+
+    def const(name):
+        n = ir.nodes[name]
+        assert n.op == "Const", (name, n.op)
+        return torch.from_numpy(np.array(n.attrs["value"]))
+    prog = compile_program(from_graph_def(g.graph), [f + ":0" for f in feeds], [fetch + ":0"], device=DEV,
+                           passes=FU.default_passes())
+    return prog, const
+
+
+def _only_impl(prog, op):
+    # (a builder's named output; the ViT front's batch scalar, PatchTokens' second input)
+    hist = {k: v for k, v in prog.op_histogram().items() if k not in ("Identity", "Shape", "StridedSlice")}
+    assert hist == {op: 1}, hist
+    return _impls(prog, op)[0]
+
+
+def bf_values(*shape, seed, scale=1.0):
+    return rnd(*shape, scale=scale, seed=seed).to(BF).float()
+
+
+def test_graph_depthwise_bn_relu6(picks, launches):
+    from test_mobilenet_fusion import _dw_graph
+    g, _fetches = _dw_graph(c=8)
+    prog, const = _compiled(g, ["x"])
+    op = _only_impl(prog, "_FusedDepthwiseConv2D")
+    assert (op.kh, op.kw, op.sh, op.sw, op.padding, op.act, op.c) == (3, 3, 1, 1, "SAME", "relu6", 8)
+    w = const("w").reshape(3, 3, 8)
+    params = tuple(const(k) for k in ("gamma", "beta", "mean", "var"))
+    w64, b64, bslack, _s, _t = _fold64(w, torch.zeros(8), params)
+    # the filter stays fp32: w * scale, the scale's 3.5 roundings and the product's -> 5 2^-24 |w'|
+    kb.assert_within(op.w, w64, 5 * kb.U_F32 * w64.abs(), "depthwise filter folded with BN")
+    kb.assert_within(op.b, b64, bslack, "depthwise bias folded with BN")
+    x = bf_values(2, 9, 9, 8, seed=3, scale=3.0)
+    y = prog.run([dev(x)])[0]
+    assert dict(launches) == {"dwconv2d": 1} and picks.choices[-1]["key"][0] == "dwconv"
+    ref, bound = fr.dw_ref(x, op.w.cpu(), op.b.cpu(), (1, 1), "SAME", act="relu6")
+    within("graph depthwise+BN+ReLU6", y, ref, bound, "output")
+
+
+def test_graph_convnext_opening(picks, launches):
+    from test_convnext_fusion import _dwln_graph
+    g, _fetches = _dwln_graph(c=8)
+    prog, const = _compiled(g, ["x"])
+    op = _only_impl(prog, "_FusedDepthwiseLN")
+    w, b, gm, bt = const("dw").reshape(7, 7, 8), const("b"), const("ln/gamma"), const("ln/beta")
+    assert fr.same_bits(op.dw.w.cpu(), w) and fr.same_bits(op.dw.b.cpu(), b)
+    assert fr.same_bits(op.ln.g.cpu(), gm) and fr.same_bits(op.ln.b.cpu(), bt)
+    assert abs(op.eps - 1e-6) < 1e-12 and (op.dw.padding, op.dw.act) == ("SAME", "none")
+    x = bf_values(2, 9, 10, 8, seed=4)
+    y = prog.run([dev(x)])[0]
+    assert dict(launches) == {"dwconv_ln": 1}
+    ref, bound = fr.dwln_ref(x, w, b, gm, bt, op.eps, "SAME")
+    within("graph ConvNeXt opening", y, ref, bound, "output")
+
+
+def test_graph_squeeze_excite(picks):
+    import se_bounds as sb
+    from test_mobilenet_v3_fusion import _se_graph
+    g, _fetches, _feeds = _se_graph(c=8, cr=4)
+    prog, const = _compiled(g, ["x"])
+    op = _only_impl(prog, "_SqueezeExcite")
+    w1, b1, w2, b2 = const("w1").reshape(8, 4), const("b1"), const("w2").reshape(4, 8), const("b2")
+    assert fr.same_bits(op.w1.cpu().reshape(8, 4), w1) and fr.same_bits(op.w2.cpu().reshape(4, 8), w2)
+    assert fr.same_bits(op.b1.cpu(), b1) and fr.same_bits(op.b2.cpu(), b2)
+    x = bf_values(2, 5, 5, 8, seed=12, scale=2.0)
+    y = prog.run([dev(x)])[0]
+    assert y.dtype == BF
+    ref, bound = sb.se_op_ref(x, w1, b1, w2, b2, "relu")
+    within("graph squeeze-excite", y, ref, bound, "output")
+
+
+@pytest.mark.parametrize("kw", [dict(), dict(pos_shape=(7, 8))], ids=["pos-rank-3", "pos-rank-2"])
+def test_graph_vit_front(picks, launches, kw):
+    from test_vit_fusion import _front_graph
+    g, _fetches, shape = _front_graph(**kw)
+    prog, const = _compiled(g, ["x"])
+    op = _only_impl(prog, "_PatchTokens")
+    cls, pos = const("cls"), const("pos")
+    table = pos.reshape(7, 8).clone()
+    table[0] += cls.reshape(8)                                       # the op's one fp32 addition
+    assert fr.same_bits(op.table.cpu(), table) and (op.p, op.c, op.pos_rank) == (6, 8, pos.dim())
+    x = bf_values(*shape, seed=5)
+    y = prog.run([dev(x)])[0]
+    assert dict(launches) == {"patch_tokens": 1} and tuple(y.shape) == (2, 7, 8)
+    ref, bound = fr.patch_tokens_ref(x, cls, pos, 2)
+    within("graph ViT front", y, ref, bound, "output")
+
+
+def test_graph_shifted_swin_block(picks, launches):
+    """The block keeps its QKV and projection GEMMs; fold_window_layout leaves ONE _WindowAttention that reads
+    image-order rows.  It is bounded on the QKV rows the program itself handed it (as ChainConv's second
+    output is bounded from the op's own first)."""
+    from test_swin_fusion import _block_graph
+    g, _fetches, feeds = _block_graph(shift=2)
+    prog, const = _compiled(g, ["x"])
+    hist = prog.op_histogram()
+    assert hist.get("_WindowAttention") == 1 and not {"Roll", "Transpose", "Softmax", "BatchMatMulV2"} & set(hist), hist
+    node = next(n for _fn, n, _i, _o in prog.steps if n.op == "_WindowAttention")
+    op = node.attrs["_impl"]
+    bias, mask = const("bias").reshape(2, 16, 16), const("mask").reshape(4, 16, 16)
+    assert op.grid == (8, 8, 4, 2) and (op.h, op.d, op.s, op.nw) == (2, 32, 16, 4)
+    assert fr.same_bits(op.bias.cpu(), bias) and fr.same_bits(op.mask.cpu(), mask)
+    seen = {}
+
+    def recording(ctx, n, ins):
+        outs = op(ctx, n, ins)
+        seen["qkv"], seen["y"] = ins[0].detach().cpu(), outs[0].detach().cpu()
+        return outs
+    node.attrs["_impl"] = recording
+    x = bf_values(*feeds["x"].shape, seed=6)
+    out = prog.run([dev(x)])[0]
+    assert tuple(out.shape) == tuple(x.shape) and dict(launches).get("window_attention") == 1
+    qkv = seen["qkv"].reshape(-1, 3 * 2 * 32)
+    assert qkv.dtype == BF and qkv.shape[0] == 2 * 8 * 8
+    ref, bound = fr.wattn_ref(qkv, bias, mask, 2, op.scale, (8, 8, 4, 2))
+    assert abs(op.scale - 32 ** -0.5) < 1e-6
+    within("graph shifted Swin block", seen["y"], ref, bound, "the window attention on the program's own QKV rows")
+
+
+@pytest.mark.parametrize("spelling", ["split", "separate", "concat"])
+def test_graph_dlrm_bag(picks, launches, spelling):
+    from test_dlrm_fusion import _bag_graph
+    vocab, hot = (4, 6), (1, 3)
+    g, _fetches, feeds = _bag_graph(spelling=spelling, vocab=vocab, hot=hot)
+    prog, const = _compiled(g, list(feeds))
+    op = _only_impl(prog, "_EmbeddingBag")
+    tables = [const(f"table{f}") for f in range(2)]
+    assert fr.same_bits(op.blob.cpu(), torch.cat(tables, 0).to(BF)), "the blob: every table rounded once"
+    assert (op.vocab, op.lead, op.split) == ([4, 6], True, None if spelling == "separate" else [1, 3])
+    ids, _t, dense = fr.bag_case_inputs(vocab, hot, 8, 3, lead=True)
+    ins = {"x0": dev(dense), "sparse": dev(ids)}
+    ins.update({f"ids{f}": dev(i.contiguous()) for f, i in enumerate(torch.split(ids, list(hot), 1))})
+    y = prog.run([ins[k] for k in feeds])[0]
+    assert dict(launches) == {"embedding_bag": 1} and tuple(y.shape) == (3, 3, 8)
+    ref, bound = fr.bag_ref(ids, [t.to(BF).float() for t in tables], hot, dense)
+    within("graph DLRM bag", y, ref, bound, f"output ({spelling})")
+
+
+@pytest.mark.parametrize("k,pad", [(-1, 1), (0, 0)])
+def test_graph_dlrm_interaction(picks, launches, k, pad):
+    from test_dlrm_fusion import _interact_graph
+    g, _fetches, feeds = _interact_graph(f=5, d=32, dd=8, k=k, pad=pad)
+    prog, _const = _compiled(g, list(feeds))
+    op = _only_impl(prog, "_DotInteraction")
+    assert (op.f, op.self_interaction, op.pad) == (5, k == 0, pad)
+    assert op.idx.cpu().tolist() == [i * 5 + j for i, j in fr.tril_order(5, k == 0)]
+    z, dense = fr.interact_case_inputs(3, 5, 32, dd=8)
+    y = prog.run([dev({"z": z, "dense": dense}[n].float()) for n in feeds])[0]
+    assert dict(launches) == {"dot_interaction": 1} and tuple(y.shape) == (3, 8 + len(op.idx) + pad)
+    ref, bound = fr.interact_ref(z, dense, k == 0, pad)
+    within("graph DLRM interaction", y, ref, bound, "output")
+
+
 def test_zz_report_worst_ratios():
-    """Not a check: writes the worst err / bound per op class and the
-    candidates each case rejected when asked to."""
+    """Not a check: writes the worst err / bound per op class, the candidates
+    each case rejected and the module's run time so far when asked to."""
     path = os.environ.get("FUSED_OPS_REPORT")
     if path:
         with open(path, "w") as f:
-            json.dump({"worst": dict(sorted(WORST.items())), "rejected": REJECTED}, f, indent=1)
+            json.dump({"worst": dict(sorted(WORST.items())), "rejected": REJECTED,
+                       "seconds": round(time.perf_counter() - CLOCK["t0"], 2)}, f, indent=1)
     assert all(v <= 1.0 for v in WORST.values())

@@ -20,6 +20,7 @@ import pytest
 import torch
 
 import kernel_bounds as kb
+from patch_tokens_bounds import reference
 
 pytestmark = pytest.mark.gpu
 
@@ -36,19 +37,6 @@ def operands(b, p, c, seed=0):
     x = kb.rnd(b, p, c, seed=seed + 1).to(BF)
     table = kb.rnd(p + 1, c, scale=0.5, seed=seed + 2)
     return x, table
-
-
-def reference(x, table):
-    """(ref, bound) [B, P + 1, C] in fp64."""
-    b, p, c = x.shape
-    t = kb.d(table)
-    ref = torch.cat([t[0].expand(b, 1, c), kb.d(x) + t[1:]], dim=1)
-    mag = ref.abs() * (1 + kb.E)
-    half_ulp = torch.where(mag > 0, torch.exp2(torch.floor(torch.log2(mag.clamp_min(1e-300))) - 8),
-                           torch.zeros_like(mag))
-    # the class row is one rounding of T[0] itself (no add)
-    bound = half_ulp + kb.E * ref.abs()
-    return ref, bound
 
 
 @pytest.mark.parametrize("b", [1, 3])
