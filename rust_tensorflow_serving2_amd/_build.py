@@ -61,6 +61,11 @@ def _local_includes(src, headers):
     return sorted(seen)
 
 
+# Flags of single sources, by file name.  cattn.hip: no packed-fp32 VALU ops
+# (the compiler pairs the softmax's scalar fp32 arithmetic otherwise).
+SOURCE_FLAGS = {"cattn.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+
+
 def _compile_all(compiler, sources, headers, flags, tag, jobs):
     os.makedirs(BUILD, exist_ok=True)
     objs, todo = [], []
@@ -68,14 +73,15 @@ def _compile_all(compiler, sources, headers, flags, tag, jobs):
         base = os.path.splitext(os.path.basename(src))[0]
         obj = os.path.join(BUILD, f"{tag}_{base}.o")
         stamp = obj + ".sha1"
-        d = _digest([src] + _local_includes(src, headers), flags + [compiler])
+        own = flags + SOURCE_FLAGS.get(os.path.basename(src), [])
+        d = _digest([src] + _local_includes(src, headers), own + [compiler])
         if not (os.path.exists(obj) and os.path.exists(stamp) and open(stamp).read() == d):
-            todo.append((src, obj, stamp, d))
+            todo.append((src, obj, own, stamp, d))
         objs.append(obj)
 
     def work(item):
-        src, obj, stamp, d = item
-        _run([compiler] + flags + ["-c", src, "-o", obj])
+        src, obj, own, stamp, d = item
+        _run([compiler] + own + ["-c", src, "-o", obj])
         with open(stamp, "w") as f:
             f.write(d)
         return src

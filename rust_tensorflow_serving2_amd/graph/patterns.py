@@ -14,6 +14,10 @@
       y = Reshape(Transpose(BatchMatMul(p, v), [0,2,1,3]), [-1, H*D])
         => _FusedQKV(x)  (one GEMM, concatenated weights)  ->  _Attention(qkv, mask_adder)
 
+* GPT-2's causal attention (``fuse_causal_attention``): the mask spelled ``w * b - fill * (1 - b)`` or
+  ``SelectV2(b, w, fill)`` over the lower-triangular band b, q / k / v from one packed dense
+        => _FusedQKV(x)  ->  _CausalAttention(qkv, key_adder)
+
 * Swin's windowed attention (``fuse_window_attention``) and the roll / partition /
   reverse layout around it (``fold_window_layout``)
         => _FusedQKV(x)  ->  _WindowAttention(qkv; bias, mask, grid)
@@ -763,6 +767,212 @@ def fuse_window_attention(g, order, fed, fetch_refs, device, opts):
         c.refresh()
 
 
+# ------------------------------------------------------------------ causal attention (GPT-2)
+MIN_CAUSAL_FILL = 1e4         # a smaller |fill| leaves a masked key a visible share of the softmax
+
+
+class CausalAttentionOp:
+    """softmax(mask(q k^T * scale) (+ adder)) v over a packed QKV buffer, mask =
+    keep the score where key <= query, else ``closed`` (the matched graph's
+    ``-fill`` of ``w * b - fill * (1 - b)``, or the ``fill`` of ``SelectV2``).
+
+    On the device, for D = 64 and an adder that is absent or [B | 1, 1, 1, S],
+    one ``causal_attention`` launch (kernels/cattn.hip), which closes masked
+    keys with -inf instead of ``closed``: equal to rounding wherever a row has
+    an open key whose adder is 0 (docs/numerics.md, "Causal attention").
+    Anywhere else the graph's own arithmetic with torch, in fp32."""
+
+    def __init__(self, heads: int, head_dim: int, seq: int, scale: float, closed: float, use_hip: bool):
+        self.h, self.d, self.s, self.scale, self.closed, self.use_hip = heads, head_dim, seq, scale, closed, use_hip
+
+    def __call__(self, ctx, node, ins):
+        qkv = O.to_torch(ins[0])
+        adder = O.to_torch(ins[1]) if len(ins) > 1 else None
+        S, H, D = self.s, self.h, self.d
+        if qkv.numel() % (S * 3 * H * D):
+            raise O.OpError(f"{node.name}: {list(qkv.shape)} is not [B * {S}, {3 * H * D}]")
+        B = qkv.numel() // (S * 3 * H * D)
+        key_adder = adder is None or (adder.dim() == 4 and tuple(adder.shape[1:]) == (1, 1, S) and
+                                      adder.shape[0] in (1, B))
+        if self.use_hip and qkv.is_cuda and D == 64 and 1 <= S <= MAX_ATTENTION_SEQ and key_adder:
+            from ..ops import hip
+            from .fused import _to_bf16
+            q3 = _to_bf16(qkv).reshape(B, S, 3 * H * D).contiguous()
+            ka = None if adder is None else adder.float().reshape(-1, S).contiguous().to(qkv.device)
+            return [hip().causal_attention(q3, ka, H, self.scale).reshape(B * S, H * D)]
+        q, k, v = qkv.float().reshape(B, S, 3, H, D).permute(2, 0, 3, 1, 4)
+        sc = q @ k.transpose(-1, -2) * self.scale
+        band = torch.ones(S, S, dtype=torch.bool, device=sc.device).tril()
+        sc = torch.where(band, sc, torch.full_like(sc, self.closed))
+        if adder is not None:
+            sc = sc + adder.float().to(sc.device)
+        y = (torch.softmax(sc, -1) @ v).permute(0, 2, 1, 3).reshape(B * S, H * D)
+        return [y if not qkv.is_cuda else y.to(qkv.dtype)]
+
+
+def _square(v: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+    """A constant shaped [S, S] under at most two leading 1s -> it as [S, S], else None."""
+    if v is None or v.dim() < 2 or v.dim() > 4 or v.shape[-1] != v.shape[-2] or v.numel() != v.shape[-1] ** 2:
+        return None
+    return v.reshape(v.shape[-1], v.shape[-1])
+
+
+def _causal_mask(g, n: Optional[Node]):
+    """n = Sub(Mul(w, b), c) or SelectV2(b, w, fill) with b the exact lower-triangular band
+    -> (w ref, S, the value of a masked score, nodes), else None."""
+    if n is None:
+        return None
+    if n.op == "SelectV2" and len(n.inputs) == 3:
+        b, fill = _square(_const_t(g, n.inputs[0])), _const_t(g, n.inputs[2])
+        if b is None or b.dtype != torch.bool or fill is None or fill.numel() != 1 or not fill.is_floating_point():
+            return None
+        closed, w_ref, nodes = float(fill), n.inputs[1], [n]
+        if not closed <= -MIN_CAUSAL_FILL:
+            return None
+    elif n.op == "Sub" and len(n.inputs) == 2:
+        mul, cv = _node(g, n.inputs[0]), _square(_const_t(g, n.inputs[1]))
+        if mul is None or mul.op != "Mul" or len(mul.inputs) != 2 or cv is None or not cv.is_floating_point():
+            return None
+        for k in (0, 1):
+            b = _square(_const_t(g, mul.inputs[k]))
+            if b is not None:
+                break
+        else:
+            return None
+        if not b.is_floating_point() or b.shape != cv.shape:
+            return None
+        # c = fill * (1 - b): zero on the band, one value everywhere above it
+        fill = float(cv[0, -1]) if cv.shape[0] > 1 else MIN_CAUSAL_FILL
+        if not fill >= MIN_CAUSAL_FILL or not torch.equal(cv.double(), fill * (1.0 - b.double())):
+            return None
+        closed, w_ref, nodes = -fill, mul.inputs[1 - k], [n, mul]
+    else:
+        return None
+    if not torch.equal(b.double(), torch.ones(b.shape, dtype=torch.float64).tril()):
+        return None
+    return w_ref, int(b.shape[0]), closed, nodes
+
+
+def _split_qkv(g, c, refs, H: int, D: int):
+    """refs = outputs 0, 1, 2 of Split(axis = last, num_split = 3) | SplitV(equal sizes) over
+    [Reshape of] one dense 3 * H * D wide -> (x ref, w, b, nodes), else None."""
+    sp = g.nodes.get(refs[0][0])
+    if sp is None or list(refs) != [(sp.name, 0), (sp.name, 1), (sp.name, 2)]:
+        return None
+    if sp.op == "Split" and len(sp.inputs) == 2 and int(sp.attr("num_split", 0)) == 3:
+        axis, src = _ints(g, sp.inputs[0]), sp.inputs[1]
+    elif sp.op == "SplitV" and len(sp.inputs) == 3 and _ints(g, sp.inputs[1]) == [H * D] * 3:
+        axis, src = _ints(g, sp.inputs[2]), sp.inputs[0]
+    else:
+        return None
+    nodes, rank = [sp], 2
+    r = _node(g, src)
+    if r is not None and r.op == "Reshape":
+        shp = _ints(g, r.inputs[1])
+        if shp is None or not shp or shp[-1] != 3 * H * D:
+            return None
+        nodes.append(r)
+        rank, src = len(shp), r.inputs[0]
+    if axis is None or len(axis) != 1 or axis[0] not in (-1, rank - 1):
+        return None
+    ds = _dense_src(g, c, src)
+    if ds is None or ds[1].shape[1] != 3 * H * D:
+        return None
+    return ds[0], ds[1], ds[2], nodes + ds[3]
+
+
+def fuse_causal_attention(g, order, fed, fetch_refs, device, opts):
+    """GPT-2's attention core -> _FusedQKV -> _CausalAttention::
+
+        w = BatchMatMul(q, k, adj_y)  [Mul by c | RealDiv by c: _scale_of]
+        masked = Sub(Mul(w, b), c)            b the constant lower-triangular 0/1 band [S, S] under leading 1s,
+               | SelectV2(b, w, fill)         c = fill * (1 - b) with fill >= 1e4  |  b bool, scalar fill <= -1e4
+        scores = masked | AddV2(masked, adder)                      (adder: anything but the pattern's own nodes)
+        y = Reshape(Transpose(BatchMatMul(Softmax(scores), v), [0, 2, 1, 3]), [-1, H * D])
+
+    q, k, v from three denses on one input (``_heads_of`` + ``_dense_src``) or
+    from one dense split three ways (``_split_qkv``).  Runs before
+    fuse_attention and takes nothing it takes: that pass has no Sub or SelectV2
+    under the Softmax, and a constant [1, 1, S, S] adder added to the scores stays
+    its ``_Attention``.  Anything that is not exactly the band (upper-triangular,
+    a hole, offset by one, another S), a weaker fill, a ``c`` that is not
+    fill * (1 - b), or an interior node read elsewhere is left alone."""
+    from .fused import FusedMatMul, _Ctx
+    c = _Ctx(g, order, fed, fetch_refs, device, opts)
+    for name in list(order):
+        out = g.nodes.get(name)
+        if out is None or out.op != "Reshape":
+            continue
+        t2 = _node(g, out.inputs[0])
+        if t2 is None or t2.op != "Transpose" or _ints(g, t2.inputs[1]) != [0, 2, 1, 3]:
+            continue
+        pv = _node(g, t2.inputs[0])
+        if pv is None or pv.op not in _BMM or pv.attr("adj_x", False) or pv.attr("adj_y", False):
+            continue
+        sm = _node(g, pv.inputs[0])
+        if sm is None or sm.op != "Softmax":
+            continue
+        interior = [t2, pv, sm]
+        cur = _node(g, sm.inputs[0])
+        adder_ref = None
+        if cur is not None and cur.op in ("Add", "AddV2") and len(cur.inputs) == 2:
+            for k in (0, 1):
+                side = _node(g, cur.inputs[k])
+                if side is not None and side.op in ("Sub", "SelectV2") and _causal_mask(g, side) is not None:
+                    break
+            else:
+                continue
+            adder_ref = cur.inputs[1 - k]
+            interior.append(cur)
+            cur = side
+        cm = _causal_mask(g, cur)
+        if cm is None:
+            continue
+        w_ref, S, closed, nodes = cm
+        interior += nodes
+        scale = 1.0
+        qk = _node(g, w_ref)
+        sv = _scale_of(g, qk) if qk is not None and qk.op in ("Mul", "RealDiv") else None
+        if sv is not None:
+            scale = sv[0]
+            interior.append(qk)
+            qk = _node(g, sv[1])
+        if qk is None or qk.op not in _BMM or qk.attr("adj_x", False) or not qk.attr("adj_y", False):
+            continue
+        interior.append(qk)
+        hq, hk, hv = _heads_of(g, c, qk.inputs[0]), _heads_of(g, c, qk.inputs[1]), _heads_of(g, c, pv.inputs[1])
+        if hq is None or hk is None or hv is None or hq[1:4] != hk[1:4] or hq[1:4] != hv[1:4]:
+            continue
+        H, D = hq[2], hq[3]
+        if hq[1] != S or _ints(g, out.inputs[1]) != [-1, H * D]:
+            continue                  # (the op returns [B * S, H * D])
+        interior += hq[4] + hk[4] + hv[4]
+        if adder_ref is not None and adder_ref[0] in {n.name for n in interior}:
+            continue
+        packed = _split_qkv(g, c, [hq[0], hk[0], hv[0]], H, D)
+        if packed is not None:
+            x_ref, w, b, qkv_nodes = packed
+        else:
+            dq, dk, dv = _dense_src(g, c, hq[0]), _dense_src(g, c, hk[0]), _dense_src(g, c, hv[0])
+            if not (dq and dk and dv and dq[0] == dk[0] == dv[0]) or any(d[1].shape[1] != H * D for d in (dq, dk, dv)):
+                continue
+            x_ref = dq[0]
+            w = torch.cat([dq[1], dk[1], dv[1]], dim=1)
+            b = torch.cat([dq[2], dk[2], dv[2]])
+            qkv_nodes = dq[3] + dk[3] + dv[3]
+        if not _interior_ok(c, interior + qkv_nodes, out):
+            continue
+        qkv_name = g.unique_name(out.name + "/fused_qkv")
+        g.add(Node(name=qkv_name, op="_FusedQKV", inputs=[x_ref],
+                   attrs={"_impl": FusedMatMul(w, b, "none", False, device, c.use_hip, qkv_name)}))
+        _remove(g, interior + qkv_nodes)
+        out.op = "_CausalAttention"
+        out.inputs = [(qkv_name, 0)] + ([adder_ref] if adder_ref is not None else [])
+        out.ctrl = []
+        out.attrs = {"_impl": CausalAttentionOp(H, D, S, scale, closed, c.use_hip)}
+        c.refresh()
+
+
 def _reshape_to(g, n: Optional[Node], want: Sequence[int]) -> bool:
     return n is not None and n.op == "Reshape" and _ints(g, n.inputs[1]) == list(want)
 
@@ -1459,7 +1669,8 @@ def dlrm_passes():
 
 
 def bert_passes():
-    return [fuse_layernorm, fuse_embedding, fuse_window_attention, fold_window_layout, fuse_attention, fuse_key_mask]
+    return [fuse_layernorm, fuse_embedding, fuse_window_attention, fold_window_layout, fuse_causal_attention, fuse_attention,
+            fuse_key_mask]
 
 
 def late_passes():

@@ -1124,6 +1124,41 @@ Tensor attention(const Tensor& qkv, const c10::optional<Tensor>& mask_bias, int6
   return y;
 }
 
+Tensor causal_attention(const Tensor& qkv, const c10::optional<Tensor>& key_adder, int64_t heads, double scale,
+                        const c10::optional<Tensor>& out, int64_t qb) {
+  need(qkv, at::kBFloat16, "qkv");
+  TORCH_CHECK(qkv.dim() == 3, "causal_attention: qkv must be [B, S, 3*H*D]");
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(qkv.device());
+  const int64_t B = qkv.size(0), S = qkv.size(1), HD3 = qkv.size(2);
+  TORCH_CHECK(heads >= 1 && HD3 % (3 * heads) == 0, "causal_attention: qkv width must be 3*heads*head_dim");
+  const int64_t D = HD3 / (3 * heads);
+  TORCH_CHECK(D == 64, "causal_attention kernel supports head_dim 64, got ", D);
+  TORCH_CHECK(tfsk::causal_attention_supported(S, D), "causal_attention kernel supports 1 <= S <= ",
+              tfsk::kMaxAttentionSeq, ", got S = ", S);
+  TORCH_CHECK(qb == 0 || qb == 64 || qb == 128, "causal_attention: qb must be 0, 64 or 128");
+  TORCH_CHECK(S * HD3 * 2 < (int64_t(1) << 31) && B * heads < (int64_t(1) << 31),
+              "causal_attention: one image's qkv rows exceed 2 GiB");
+  TORCH_CHECK(aligned16(qkv), "causal_attention: qkv must be 16-byte aligned");
+  const float* ap = nullptr;
+  int64_t bstride = 0;
+  if (key_adder.has_value()) {
+    need(*key_adder, at::kFloat, "key_adder");
+    TORCH_CHECK(key_adder->dim() == 2 && key_adder->size(1) == S && (key_adder->size(0) == B || key_adder->size(0) == 1),
+                "causal_attention: key_adder must be [B, S] or [1, S]");
+    TORCH_CHECK(key_adder->device() == qkv.device(), "causal_attention: key_adder is on another device");
+    bstride = key_adder->size(0) == 1 ? 0 : S;
+    ap = key_adder->data_ptr<float>();
+  }
+  Tensor y = out.has_value() ? *out : torch::empty({B, S, heads * D}, qkv.options());
+  need(y, at::kBFloat16, "out");
+  TORCH_CHECK(y.device() == qkv.device() && y.numel() == B * S * heads * D, "causal_attention: out has the wrong size");
+  TORCH_CHECK(aligned16(y), "causal_attention: out must be 16-byte aligned");
+  check(tfsk::causal_attention_launch(bf16p(qkv), ap, bf16p_mut(y), int(B), int(S), int(heads), int(D), float(scale),
+                                      bstride, cur_stream(qkv), int(qb)),
+        "causal_attention");
+  return y;
+}
+
 // the (Hf, Wf, ws, shift) of a window_attention grid argument, zeros for None
 struct WattnGrid { int64_t Hf = 0, Wf = 0, ws = 0, shift = 0; };
 WattnGrid wattn_grid(const c10::optional<std::vector<int64_t>>& grid) {
@@ -1447,6 +1482,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     const int k = tfsk::attention_forms(int(std::min<int64_t>(std::max<int64_t>(S, 0), 1 << 30)), forms);
     return std::vector<int64_t>(forms, forms + k);
   }, "the forms attention takes at length S: [0], or [0, 1] where the ragged register kernel applies");
+  m.def("causal_attention", &causal_attention, py::arg("qkv"), py::arg("key_adder") = py::none(), py::arg("heads"),
+        py::arg("scale"), py::arg("out") = py::none(), py::arg("qb") = 0,
+        "causal attention over packed qkv [B, S, 3*H*64]: the mask key <= query is computed from indices and the key "
+        "blocks above the diagonal are skipped; key_adder an optional f32 [B, S] | [1, S]; qb = query rows per "
+        "workgroup (64 / 128, 0: the default, 64)");
+  m.def("causal_attention_supported",
+        [](int64_t S, int64_t D) { return tfsk::causal_attention_supported(S, D); }, py::arg("S"), py::arg("D"),
+        "whether causal_attention takes length S with heads of width D");
   m.def("window_attention", &window_attention, py::arg("qkv"), py::arg("bias"), py::arg("mask"), py::arg("heads"),
         py::arg("scale"), py::arg("out") = py::none(), py::arg("grid") = py::none(),
         "windowed attention (Swin): S <= 64 tokens per window, 32-wide heads, per-head bias [H, S, S], optional "

@@ -345,6 +345,18 @@ void attention_set_trace(long long* trace, int cap);
 // registers (default), -1 = env TFSERVE_ATTN_PLDS; returns the previous mode
 int attention_set_plds(int mode);
 
+// Causal attention (kernels/cattn.hip) over the same packed QKV buffer:
+// ctx[b,q,h,:] = softmax over key <= q of (Q K^T * scale + key_adder[b*adder_bstride + key]) V.
+// The causal mask is computed from indices and the key blocks above the
+// diagonal are skipped; key_adder is an optional f32 [B][S] (adder_bstride = S)
+// or [1][S] (adder_bstride = 0) per-key adder, null for none.  D = 64,
+// 1 <= S <= kMaxAttentionSeq, qkv and ctx 16-B aligned, one image's qkv rows
+// below 2 GiB; qb = query rows per workgroup (64 / 128; 0: the default, 64).
+// Anything else is hipErrorInvalidValue and launches nothing.
+constexpr bool causal_attention_supported(int64_t S, int64_t D) { return D == 64 && S >= 1 && S <= kMaxAttentionSeq; }
+hipError_t causal_attention_launch(const uint16_t* qkv, const float* key_adder, uint16_t* ctx, int B, int S, int H,
+                                   int D, float scale, long adder_bstride, hipStream_t stream, int qb = 0);
+
 // Windowed attention (Swin) over a packed QKV buffer [R][3*H*32] (bf16):
 // out[row, h, :] = softmax(Q K^T * scale + bias[h] (+ mask[w])) V within each
 // window of S <= 64 tokens; bias f32 [H][S][S], mask f32 [nW][S][S] or null.
