@@ -18,6 +18,11 @@
   ``SelectV2(b, w, fill)`` over the lower-triangular band b, q / k / v from one packed dense
         => _FusedQKV(x)  ->  _CausalAttention(qkv, key_adder)
 
+* Llama's block (``fuse_rmsnorm``, ``fuse_rope_attention``, ``fuse_swiglu``): RMSNorm spelled ``Square`` / ``Mean`` /
+  ``Rsqrt``, the causal core with q and k rotated by position and k / v repeated for their group of query heads,
+  and ``swish(x Wg) * (x Wu)``
+        => _RMSNorm(x [, residual])   _FusedQKV(x) -> _RopeGQAttention(qkv, key_adder)   _FusedMatMul -> _SwiGLU
+
 * Swin's windowed attention (``fuse_window_attention``) and the roll / partition /
   reverse layout around it (``fold_window_layout``)
         => _FusedQKV(x)  ->  _WindowAttention(qkv; bias, mask, grid)
@@ -881,6 +886,50 @@ def _split_qkv(g, c, refs, H: int, D: int):
     return ds[0], ds[1], ds[2], nodes + ds[3]
 
 
+def _causal_core(g, out: Node):
+    """out = Reshape(Transpose(BatchMatMul(Softmax(scores), v), [0, 2, 1, 3]), .) with ``scores`` the causally
+    masked, optionally scaled q k^T of fuse_causal_attention, with or without an adder
+    -> (qk node, pv node, S, scale, closed, adder ref | None, interior nodes), else None."""
+    t2 = _node(g, out.inputs[0])
+    if t2 is None or t2.op != "Transpose" or _ints(g, t2.inputs[1]) != [0, 2, 1, 3]:
+        return None
+    pv = _node(g, t2.inputs[0])
+    if pv is None or pv.op not in _BMM or pv.attr("adj_x", False) or pv.attr("adj_y", False):
+        return None
+    sm = _node(g, pv.inputs[0])
+    if sm is None or sm.op != "Softmax":
+        return None
+    interior = [t2, pv, sm]
+    cur = _node(g, sm.inputs[0])
+    adder_ref = None
+    if cur is not None and cur.op in ("Add", "AddV2") and len(cur.inputs) == 2:
+        for k in (0, 1):
+            side = _node(g, cur.inputs[k])
+            if side is not None and side.op in ("Sub", "SelectV2") and _causal_mask(g, side) is not None:
+                break
+        else:
+            return None
+        adder_ref = cur.inputs[1 - k]
+        interior.append(cur)
+        cur = side
+    cm = _causal_mask(g, cur)
+    if cm is None:
+        return None
+    w_ref, S, closed, nodes = cm
+    interior += nodes
+    scale = 1.0
+    qk = _node(g, w_ref)
+    sv = _scale_of(g, qk) if qk is not None and qk.op in ("Mul", "RealDiv") else None
+    if sv is not None:
+        scale = sv[0]
+        interior.append(qk)
+        qk = _node(g, sv[1])
+    if qk is None or qk.op not in _BMM or qk.attr("adj_x", False) or not qk.attr("adj_y", False):
+        return None
+    interior.append(qk)
+    return qk, pv, S, scale, closed, adder_ref, interior
+
+
 def fuse_causal_attention(g, order, fed, fetch_refs, device, opts):
     """GPT-2's attention core -> _FusedQKV -> _CausalAttention::
 
@@ -903,43 +952,10 @@ def fuse_causal_attention(g, order, fed, fetch_refs, device, opts):
         out = g.nodes.get(name)
         if out is None or out.op != "Reshape":
             continue
-        t2 = _node(g, out.inputs[0])
-        if t2 is None or t2.op != "Transpose" or _ints(g, t2.inputs[1]) != [0, 2, 1, 3]:
+        core = _causal_core(g, out)
+        if core is None:
             continue
-        pv = _node(g, t2.inputs[0])
-        if pv is None or pv.op not in _BMM or pv.attr("adj_x", False) or pv.attr("adj_y", False):
-            continue
-        sm = _node(g, pv.inputs[0])
-        if sm is None or sm.op != "Softmax":
-            continue
-        interior = [t2, pv, sm]
-        cur = _node(g, sm.inputs[0])
-        adder_ref = None
-        if cur is not None and cur.op in ("Add", "AddV2") and len(cur.inputs) == 2:
-            for k in (0, 1):
-                side = _node(g, cur.inputs[k])
-                if side is not None and side.op in ("Sub", "SelectV2") and _causal_mask(g, side) is not None:
-                    break
-            else:
-                continue
-            adder_ref = cur.inputs[1 - k]
-            interior.append(cur)
-            cur = side
-        cm = _causal_mask(g, cur)
-        if cm is None:
-            continue
-        w_ref, S, closed, nodes = cm
-        interior += nodes
-        scale = 1.0
-        qk = _node(g, w_ref)
-        sv = _scale_of(g, qk) if qk is not None and qk.op in ("Mul", "RealDiv") else None
-        if sv is not None:
-            scale = sv[0]
-            interior.append(qk)
-            qk = _node(g, sv[1])
-        if qk is None or qk.op not in _BMM or qk.attr("adj_x", False) or not qk.attr("adj_y", False):
-            continue
-        interior.append(qk)
+        qk, pv, S, scale, closed, adder_ref, interior = core
         hq, hk, hv = _heads_of(g, c, qk.inputs[0]), _heads_of(g, c, qk.inputs[1]), _heads_of(g, c, pv.inputs[1])
         if hq is None or hk is None or hv is None or hq[1:4] != hk[1:4] or hq[1:4] != hv[1:4]:
             continue
@@ -970,6 +986,331 @@ def fuse_causal_attention(g, order, fed, fetch_refs, device, opts):
         out.inputs = [(qkv_name, 0)] + ([adder_ref] if adder_ref is not None else [])
         out.ctrl = []
         out.attrs = {"_impl": CausalAttentionOp(H, D, S, scale, closed, c.use_hip)}
+        c.refresh()
+
+
+# ------------------------------------------------------------------ Llama: RMSNorm, RoPE + GQA attention, SwiGLU
+ROPE_GROUPS = (1, 2, 4, 8)    # kernels/launch.h rope_gqa_attention_supported
+
+
+class RMSNormOp:
+    """y = z * rsqrt(mean(z^2) + eps) * gamma over the last axis, z = x or, with two
+    inputs, x + r; then the outputs are (y, z).  On the device one ``rmsnorm``
+    launch (kernels/llama.hip) for C % 8 == 0, else the graph's arithmetic in fp32."""
+
+    def __init__(self, gamma, eps, device, use_hip):
+        self.eps, self.use_hip = float(eps), use_hip
+        self.g = to_device(gamma.float().reshape(-1).contiguous(), device)
+
+    def __call__(self, ctx, node, ins):
+        x = O.to_torch(ins[0])
+        r = O.to_torch(ins[1]) if len(ins) > 1 else None
+        cols = x.shape[-1]
+        if self.use_hip and x.is_cuda and cols % 8 == 0 and cols == self.g.numel() and \
+                (r is None or r.shape == x.shape):
+            from ..ops import hip
+            from .fused import _to_bf16
+            xb = _to_bf16(x).contiguous()
+            if r is None:
+                return [hip().rmsnorm(xb, self.g, self.eps)]
+            z = torch.empty_like(xb)
+            return [hip().rmsnorm(xb, self.g, self.eps, _to_bf16(r).contiguous(), None, z), z]
+        z = x.float() if r is None else x.float() + r.float().to(x.device)
+        y = z * torch.rsqrt((z * z).mean(-1, keepdim=True) + self.eps) * self.g.to(x.device)
+        outs = [y] if r is None else [y, z]
+        return outs if not x.is_cuda else [o.to(x.dtype) for o in outs]
+
+
+class SwiGLUOp:
+    """swish(gu[:, :F]) * gu[:, F:] after one GEMM over [W_gate | W_up]: ``swiglu``
+    (kernels/llama.hip) on the device for F % 8 == 0, else torch in fp32."""
+
+    def __init__(self, width: int, use_hip: bool):
+        self.f, self.use_hip = width, use_hip
+
+    def __call__(self, ctx, node, ins):
+        gu = O.to_torch(ins[0])
+        F_ = self.f
+        if gu.shape[-1] != 2 * F_:
+            raise O.OpError(f"{node.name}: {list(gu.shape)} is not [M, {2 * F_}]")
+        if self.use_hip and gu.is_cuda and F_ % 8 == 0:
+            from ..ops import hip
+            from .fused import _to_bf16
+            y = hip().swiglu(_to_bf16(gu).reshape(-1, 2 * F_).contiguous())
+            return [y.reshape(list(gu.shape[:-1]) + [F_])]
+        gf = gu.float()
+        gate, up = gf[..., :F_], gf[..., F_:]
+        y = gate * torch.sigmoid(gate) * up
+        return [y if not gu.is_cuda else y.to(gu.dtype)]
+
+
+class RopeGQAttentionOp:
+    """Causal attention over a packed [Q heads | K heads | V heads] buffer with
+    q and k rotated by position (rotate-half, tables ``cos`` / ``sin`` [S, D / 2])
+    and query head h reading K / V head h / G, G = heads / kv_heads; the mask and
+    the adder as in CausalAttentionOp.
+
+    On the device, for D = 64, G in {1, 2, 4, 8} and an adder that is absent or
+    [B | 1, 1, 1, S], one ``rope_gqa_attention`` launch (kernels/gqattn.hip):
+    it rotates in fp32 and rounds to bf16 once, and closes masked keys with
+    -inf (docs/numerics.md, "RoPE + GQA attention").  Anywhere else the graph's
+    own arithmetic with torch, in fp32."""
+
+    def __init__(self, heads, kv_heads, head_dim, seq, scale, closed, cos, sin, device, use_hip):
+        self.h, self.hkv, self.d, self.s = heads, kv_heads, head_dim, seq
+        self.scale, self.closed, self.use_hip = scale, closed, use_hip
+        self.cos = to_device(cos.float().contiguous(), device)
+        self.sin = to_device(sin.float().contiguous(), device)
+
+    def __call__(self, ctx, node, ins):
+        qkv = O.to_torch(ins[0])
+        adder = O.to_torch(ins[1]) if len(ins) > 1 else None
+        S, H, K, D = self.s, self.h, self.hkv, self.d
+        W = (H + 2 * K) * D
+        if qkv.numel() % (S * W):
+            raise O.OpError(f"{node.name}: {list(qkv.shape)} is not [B * {S}, {W}]")
+        B = qkv.numel() // (S * W)
+        key_adder = adder is None or (adder.dim() == 4 and tuple(adder.shape[1:]) == (1, 1, S) and
+                                      adder.shape[0] in (1, B))
+        if self.use_hip and qkv.is_cuda and D == 64 and H // K in ROPE_GROUPS and 1 <= S <= MAX_ATTENTION_SEQ and \
+                key_adder:
+            from ..ops import hip
+            from .fused import _to_bf16
+            q3 = _to_bf16(qkv).reshape(B, S, W).contiguous()
+            ka = None if adder is None else adder.float().reshape(-1, S).contiguous().to(qkv.device)
+            y = hip().rope_gqa_attention(q3, self.cos, self.sin, ka, H, K, self.scale)
+            return [y.reshape(B * S, H * D)]
+        f = qkv.float().reshape(B, S, W)
+        cos = torch.cat([self.cos, self.cos], -1).to(f.device)
+        sin = torch.cat([self.sin, self.sin], -1).to(f.device)
+
+        def heads(t, n):              # [B, S, n * D] -> [B, H, S, D], each head repeated H / n times
+            return t.reshape(B, S, n, 1, D).expand(B, S, n, H // n, D).reshape(B, S, H, D).permute(0, 2, 1, 3)
+
+        def rot(t):
+            return t * cos + torch.cat([-t[..., D // 2:], t[..., :D // 2]], -1) * sin
+        q, k = rot(heads(f[..., :H * D], H)), rot(heads(f[..., H * D:(H + K) * D], K))
+        v = heads(f[..., (H + K) * D:], K)
+        sc = q @ k.transpose(-1, -2) * self.scale
+        band = torch.ones(S, S, dtype=torch.bool, device=sc.device).tril()
+        sc = torch.where(band, sc, torch.full_like(sc, self.closed))
+        if adder is not None:
+            sc = sc + adder.float().to(sc.device)
+        y = (torch.softmax(sc, -1) @ v).permute(0, 2, 1, 3).reshape(B * S, H * D)
+        return [y if not qkv.is_cuda else y.to(qkv.dtype)]
+
+
+def fuse_rmsnorm(g, order, fed, fetch_refs, device, opts):
+    """``Mul(Mul(x, Rsqrt(AddV2(Mean(Square(x), -1, keep_dims), eps))), gamma)`` (operands in
+    either order, gamma a constant along the last axis) -> ``_RMSNorm(x)``.
+
+    When x is an ``AddV2(a, b)`` of two non-constants that is not fetched and is
+    read only by the norm and by at most one more node, itself an ``AddV2`` (the
+    next residual add), the add goes in too: ``_RMSNorm(a, b)`` with the sum as
+    output 1, which that reader takes.  An interior node read elsewhere, a Mean
+    without keep_dims or over another axis, or a gamma that is not a row leaves
+    the graph alone."""
+    from .fused import _Ctx
+    c = _Ctx(g, order, fed, fetch_refs, device, opts)
+    for name in list(order):
+        out = g.nodes.get(name)
+        if out is None or out.op != "Mul" or len(out.inputs) != 2:
+            continue
+        for k in (0, 1):
+            inner, gamma = _node(g, out.inputs[k]), _const_t(g, out.inputs[1 - k])
+            if inner is not None and inner.op == "Mul" and len(inner.inputs) == 2 and gamma is not None:
+                break
+        else:
+            continue
+        gv = _last_axis_const(gamma)
+        if gv is None or gv.numel() == 1 or not gv.is_floating_point():
+            continue
+        for k in (0, 1):
+            rs, x_ref = _node(g, inner.inputs[k]), inner.inputs[1 - k]
+            if rs is not None and rs.op == "Rsqrt":
+                break
+        else:
+            continue
+        add = _node(g, rs.inputs[0])
+        if add is None or add.op not in ("Add", "AddV2") or len(add.inputs) != 2:
+            continue
+        for k in (0, 1):
+            ms, eps = _node(g, add.inputs[k]), _scalar(g, add.inputs[1 - k])
+            if ms is not None and ms.op == "Mean" and eps is not None:
+                break
+        else:
+            continue
+        sq = _node(g, ms.inputs[0])
+        if not ms.attr("keep_dims", False) or not _axes_last(g, ms.inputs[1]) or sq is None or sq.op != "Square" or \
+                sq.inputs[0] != x_ref:
+            continue
+        interior = [inner, rs, add, ms, sq]
+        if not _interior_ok(c, interior, out):
+            continue
+        inputs = [x_ref]
+        xs = _node(g, x_ref)
+        if xs is not None and xs.op == "AddV2" and len(xs.inputs) == 2 and xs.name not in c.fetch_nodes and \
+                all(_const_t(g, r) is None for r in xs.inputs):
+            others = {cn for cn, _p, _i in c.cons.get(xs.name, [])} - {sq.name, inner.name}
+            if len(others) <= 1 and all(g.nodes[cn].op == "AddV2" for cn in others):
+                for cn in others:
+                    g.nodes[cn].inputs = [(out.name, 1) if r == x_ref else r for r in g.nodes[cn].inputs]
+                inputs = list(xs.inputs)
+                interior.append(xs)
+        _remove(g, interior)
+        out.op = "_RMSNorm"
+        out.inputs = inputs
+        out.ctrl = []
+        out.attrs = {"_impl": RMSNormOp(gv, eps, device, c.use_hip)}
+        c.refresh()
+
+
+def _rope_of(g, ref):
+    """ref = AddV2(Mul(x, cos), Mul(ConcatV2(Neg(x2), x1, axis = -1), sin)) with x1, x2 = Split(x, 2, axis = -1)
+    and cos, sin constants [S, D] under leading 1s whose two halves are equal
+    -> (x ref, cos [S, D / 2], sin [S, D / 2], nodes), else None."""
+    add = _node(g, ref)
+    if add is None or add.op != "AddV2" or len(add.inputs) != 2:
+        return None
+    muls = [_node(g, r) for r in add.inputs]
+    if any(m is None or m.op != "Mul" or len(m.inputs) != 2 for m in muls):
+        return None
+
+    def table(m):                    # Mul(t, const) in either order -> (t ref, const [S, D])
+        for k in (0, 1):
+            v = _const_t(g, m.inputs[k])
+            if v is not None and v.dim() >= 2 and v.is_floating_point() and v.numel() == v.shape[-1] * v.shape[-2]:
+                return m.inputs[1 - k], v.reshape(v.shape[-2], v.shape[-1])
+        return None
+    for mc, ms in (muls, muls[::-1]):
+        tc, ts = table(mc), table(ms)
+        cat = _node(g, ts[0]) if tc is not None and ts is not None else None
+        if cat is None or cat.op != "ConcatV2" or len(cat.inputs) != 3 or _ints(g, cat.inputs[2]) != [-1]:
+            continue
+        x_ref, cos, sin = tc[0], tc[1], ts[1]
+        neg, sp = _node(g, cat.inputs[0]), g.nodes.get(cat.inputs[1][0])
+        if neg is None or neg.op != "Neg" or sp is None or sp.op != "Split" or int(sp.attr("num_split", 0)) != 2 or \
+                cat.inputs[1] != (sp.name, 0) or neg.inputs[0] != (sp.name, 1) or sp.inputs[1] != x_ref or \
+                _ints(g, sp.inputs[0]) != [-1]:
+            continue
+        half = cos.shape[1] // 2
+        if cos.shape != sin.shape or cos.shape[1] % 2 or not torch.equal(cos[:, :half], cos[:, half:]) or \
+                not torch.equal(sin[:, :half], sin[:, half:]):
+            continue
+        return x_ref, cos[:, :half], sin[:, :half], [add, mc, ms, cat, neg, sp]
+    return None
+
+
+def _group_heads_of(g, c, ref):
+    """``_heads_of`` with, under the Reshape, an optional repeat of each head for its group:
+    Reshape [-1, S, H, D] of Tile [1, 1, 1, G, 1] of Reshape [-1, S, H / G, 1, D]
+    -> (dense ref, S, H, D, heads of the dense, nodes), else None."""
+    h = _heads_of(g, c, ref)
+    if h is None:
+        return None
+    src, S, H, D, nodes = h
+    tile = _node(g, src)
+    if tile is None or tile.op != "Tile":
+        return src, S, H, D, H, nodes
+    mult, r5 = _ints(g, tile.inputs[1]), _node(g, tile.inputs[0])
+    shp = _ints(g, r5.inputs[1]) if r5 is not None and r5.op == "Reshape" else None
+    if mult is None or len(mult) != 5 or shp is None or len(shp) != 5:
+        return None
+    G = mult[3]
+    if mult != [1, 1, 1, G, 1] or G < 1 or H % G or shp != [-1, S, H // G, 1, D]:
+        return None
+    return r5.inputs[0], S, H, D, H // G, nodes + [tile, r5]
+
+
+def fuse_rope_attention(g, order, fed, fetch_refs, device, opts):
+    """Llama's attention core -> _FusedQKV -> _RopeGQAttention: fuse_causal_attention's
+    skeleton (``_causal_core``: the same masks, scale spellings and optional adder) with
+
+    * q and k each rotated by position (``_rope_of``), with the same tables, of the pattern's S;
+    * k and v each repeated for its group of query heads before the head transpose
+      (``_group_heads_of``; no Tile when the group is one head), q not;
+    * q, k, v from three denses on one input, H * D, Hkv * D and Hkv * D wide.
+
+    Runs before fuse_causal_attention and takes nothing it takes: q and k must
+    both be rotated.  A table whose halves differ, tables of another S or that
+    differ between q and k, a rotated v, a Tile on another axis, or an interior
+    node read elsewhere leaves the graph alone (fuse_causal_attention does not
+    match it either: ``_heads_of`` finds an AddV2 or a Tile)."""
+    from .fused import FusedMatMul, _Ctx
+    c = _Ctx(g, order, fed, fetch_refs, device, opts)
+    for name in list(order):
+        out = g.nodes.get(name)
+        if out is None or out.op != "Reshape":
+            continue
+        core = _causal_core(g, out)
+        if core is None:
+            continue
+        qk, pv, S, scale, closed, adder_ref, interior = core
+        rq, rk = _rope_of(g, qk.inputs[0]), _rope_of(g, qk.inputs[1])
+        if rq is None or rk is None or not torch.equal(rq[1], rk[1]) or not torch.equal(rq[2], rk[2]):
+            continue
+        hq, hk, hv = _group_heads_of(g, c, rq[0]), _group_heads_of(g, c, rk[0]), _group_heads_of(g, c, pv.inputs[1])
+        if hq is None or hk is None or hv is None or hq[1:4] != hk[1:4] or hq[1:4] != hv[1:4]:
+            continue
+        H, D, K = hq[2], hq[3], hk[4]
+        if hq[1] != S or hq[4] != H or hv[4] != K or tuple(rq[1].shape) != (S, D // 2) or \
+                _ints(g, out.inputs[1]) != [-1, H * D]:
+            continue
+        interior += rq[3] + rk[3] + hq[5] + hk[5] + hv[5]
+        if adder_ref is not None and adder_ref[0] in {n.name for n in interior}:
+            continue
+        dq, dk, dv = _dense_src(g, c, hq[0]), _dense_src(g, c, hk[0]), _dense_src(g, c, hv[0])
+        if not (dq and dk and dv and dq[0] == dk[0] == dv[0]) or \
+                [d[1].shape[1] for d in (dq, dk, dv)] != [H * D, K * D, K * D]:
+            continue
+        qkv_nodes = dq[3] + dk[3] + dv[3]
+        if not _interior_ok(c, interior + qkv_nodes, out):
+            continue
+        qkv_name = g.unique_name(out.name + "/fused_qkv")
+        w, b = torch.cat([dq[1], dk[1], dv[1]], dim=1), torch.cat([dq[2], dk[2], dv[2]])
+        g.add(Node(name=qkv_name, op="_FusedQKV", inputs=[dq[0]],
+                   attrs={"_impl": FusedMatMul(w, b, "none", False, device, c.use_hip, qkv_name)}))
+        _remove(g, interior + qkv_nodes)
+        out.op = "_RopeGQAttention"
+        out.inputs = [(qkv_name, 0)] + ([adder_ref] if adder_ref is not None else [])
+        out.ctrl = []
+        out.attrs = {"_impl": RopeGQAttentionOp(H, K, D, S, scale, closed, rq[1], rq[2], device, c.use_hip)}
+        c.refresh()
+
+
+def fuse_swiglu(g, order, fed, fetch_refs, device, opts):
+    """``Mul(_Swish(MatMul(x, Wg)), MatMul(x, Wu))`` (operands in either order; both
+    denses bias-free, on one input, equally wide, read by nothing else) ->
+    ``_FusedMatMul(x; [Wg | Wu])`` -> ``_SwiGLU``: x is read once.  Runs after
+    fuse_swish, which spells the ``x * Sigmoid(x)``."""
+    from .fused import FusedMatMul, _Ctx
+    c = _Ctx(g, order, fed, fetch_refs, device, opts)
+    for name in list(order):
+        out = g.nodes.get(name)
+        if out is None or out.op != "Mul" or len(out.inputs) != 2:
+            continue
+        for k in (0, 1):
+            sw = _node(g, out.inputs[k])
+            if sw is not None and sw.op == "_Swish":
+                break
+        else:
+            continue
+        dg, du = _dense_src(g, c, sw.inputs[0]), _dense_src(g, c, out.inputs[1 - k])
+        if not (dg and du) or dg[0] != du[0] or len(dg[3]) != 1 or len(du[3]) != 1 or dg[1].shape != du[1].shape or \
+                dg[3][0] is du[3][0]:
+            continue
+        interior = [sw] + dg[3] + du[3]
+        if not _interior_ok(c, interior, out):
+            continue
+        mm_name = g.unique_name(out.name + "/gate_up")
+        g.add(Node(name=mm_name, op="_FusedMatMul", inputs=[dg[0]],
+                   attrs={"_impl": FusedMatMul(torch.cat([dg[1], du[1]], dim=1), None, "none", False, device,
+                                               c.use_hip, mm_name)}))
+        _remove(g, interior)
+        out.op = "_SwiGLU"
+        out.inputs = [(mm_name, 0)]
+        out.ctrl = []
+        out.attrs = {"_impl": SwiGLUOp(int(dg[1].shape[1]), c.use_hip)}
         c.refresh()
 
 
@@ -1669,8 +2010,8 @@ def dlrm_passes():
 
 
 def bert_passes():
-    return [fuse_layernorm, fuse_embedding, fuse_window_attention, fold_window_layout, fuse_causal_attention, fuse_attention,
-            fuse_key_mask]
+    return [fuse_layernorm, fuse_rmsnorm, fuse_embedding, fuse_window_attention, fold_window_layout, fuse_rope_attention,
+            fuse_causal_attention, fuse_attention, fuse_key_mask, fuse_swiglu]
 
 
 def late_passes():

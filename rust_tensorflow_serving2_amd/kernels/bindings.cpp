@@ -1159,6 +1159,102 @@ Tensor causal_attention(const Tensor& qkv, const c10::optional<Tensor>& key_adde
   return y;
 }
 
+Tensor rope_gqa_attention(const Tensor& qkv, const Tensor& cos, const Tensor& sin,
+                          const c10::optional<Tensor>& key_adder, int64_t heads, int64_t kv_heads, double scale,
+                          const c10::optional<Tensor>& out) {
+  need(qkv, at::kBFloat16, "qkv");
+  need(cos, at::kFloat, "cos");
+  need(sin, at::kFloat, "sin");
+  TORCH_CHECK(qkv.dim() == 3, "rope_gqa_attention: qkv must be [B, S, (H + 2*Hkv)*D]");
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(qkv.device());
+  const int64_t B = qkv.size(0), S = qkv.size(1), W = qkv.size(2);
+  TORCH_CHECK(heads >= 1 && kv_heads >= 1 && W % (heads + 2 * kv_heads) == 0,
+              "rope_gqa_attention: qkv width must be (heads + 2*kv_heads)*head_dim");
+  const int64_t D = W / (heads + 2 * kv_heads);
+  TORCH_CHECK(D == 64, "rope_gqa_attention kernel supports head_dim 64, got ", D);
+  TORCH_CHECK(heads % kv_heads == 0 && (heads / kv_heads == 1 || heads / kv_heads == 2 || heads / kv_heads == 4 ||
+                                        heads / kv_heads == 8),
+              "rope_gqa_attention: heads / kv_heads must be 1, 2, 4 or 8, got ", heads, " / ", kv_heads);
+  TORCH_CHECK(tfsk::rope_gqa_attention_supported(S, D, heads, kv_heads), "rope_gqa_attention kernel supports 1 <= S <= ",
+              tfsk::kMaxAttentionSeq, ", got S = ", S);
+  TORCH_CHECK(S * W * 2 < (int64_t(1) << 31) && B * kv_heads < (int64_t(1) << 31),
+              "rope_gqa_attention: one image's qkv rows exceed 2 GiB");
+  TORCH_CHECK(aligned16(qkv), "rope_gqa_attention: qkv must be 16-byte aligned");
+  TORCH_CHECK(cos.dim() == 2 && cos.size(0) == S && cos.size(1) == D / 2 && sin.dim() == 2 && sin.size(0) == S &&
+                  sin.size(1) == D / 2,
+              "rope_gqa_attention: cos / sin must be [S, ", D / 2, "]");
+  TORCH_CHECK(cos.device() == qkv.device() && sin.device() == qkv.device(),
+              "rope_gqa_attention: cos / sin are on another device");
+  TORCH_CHECK(aligned16(cos) && aligned16(sin), "rope_gqa_attention: cos / sin must be 16-byte aligned");
+  const float* ap = nullptr;
+  int64_t bstride = 0;
+  if (key_adder.has_value()) {
+    need(*key_adder, at::kFloat, "key_adder");
+    TORCH_CHECK(key_adder->dim() == 2 && key_adder->size(1) == S && (key_adder->size(0) == B || key_adder->size(0) == 1),
+                "rope_gqa_attention: key_adder must be [B, S] or [1, S]");
+    TORCH_CHECK(key_adder->device() == qkv.device(), "rope_gqa_attention: key_adder is on another device");
+    bstride = key_adder->size(0) == 1 ? 0 : S;
+    ap = key_adder->data_ptr<float>();
+  }
+  Tensor y = out.has_value() ? *out : torch::empty({B, S, heads * D}, qkv.options());
+  need(y, at::kBFloat16, "out");
+  TORCH_CHECK(y.device() == qkv.device() && y.numel() == B * S * heads * D, "rope_gqa_attention: out has the wrong size");
+  TORCH_CHECK(aligned16(y), "rope_gqa_attention: out must be 16-byte aligned");
+  check(tfsk::rope_gqa_attention_launch(bf16p(qkv), cos.data_ptr<float>(), sin.data_ptr<float>(), ap, bf16p_mut(y),
+                                        int(B), int(S), int(heads), int(kv_heads), int(D), float(scale), bstride,
+                                        cur_stream(qkv)),
+        "rope_gqa_attention");
+  return y;
+}
+
+Tensor rmsnorm(const Tensor& x, const Tensor& gamma, double eps, const c10::optional<Tensor>& residual,
+               const c10::optional<Tensor>& out, const c10::optional<Tensor>& sum_out) {
+  need(x, at::kBFloat16, "x");
+  need(gamma, at::kFloat, "gamma");
+  TORCH_CHECK(x.dim() >= 1, "rmsnorm: x must be [rows, C]");
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
+  const int64_t cols = x.size(-1);
+  TORCH_CHECK(cols >= 8 && cols % 8 == 0 && gamma.numel() == cols, "rmsnorm: C % 8 == 0 and gamma [C], got C = ", cols,
+              " and ", gamma.numel(), " gammas");
+  TORCH_CHECK(gamma.device() == x.device(), "rmsnorm: gamma is on another device");
+  const int64_t rows = x.numel() / cols;
+  TORCH_CHECK(rows < (int64_t(1) << 31), "rmsnorm: too many rows");
+  const uint16_t* r = nullptr;
+  if (residual.has_value()) {
+    need(*residual, at::kBFloat16, "residual");
+    TORCH_CHECK(residual->numel() == x.numel() && residual->device() == x.device(), "rmsnorm: residual shape");
+    TORCH_CHECK(aligned16(*residual), "rmsnorm: residual must be 16-byte aligned");
+    r = bf16p(*residual);
+  }
+  Tensor y = out.has_value() ? *out : torch::empty_like(x);
+  need(y, at::kBFloat16, "out");
+  TORCH_CHECK(y.numel() == x.numel() && y.device() == x.device(), "rmsnorm: out has the wrong size");
+  uint16_t* sp = nullptr;
+  if (sum_out.has_value()) {
+    need(*sum_out, at::kBFloat16, "sum_out");
+    TORCH_CHECK(sum_out->numel() == x.numel() && sum_out->device() == x.device(), "rmsnorm: sum_out has the wrong size");
+    TORCH_CHECK(aligned16(*sum_out), "rmsnorm: sum_out must be 16-byte aligned");
+    sp = bf16p_mut(*sum_out);
+  }
+  TORCH_CHECK(aligned16(x) && aligned16(gamma) && aligned16(y), "rmsnorm: tensors must be 16-byte aligned");
+  check(tfsk::rmsnorm_launch(bf16p(x), r, gamma.data_ptr<float>(), bf16p_mut(y), sp, int(rows), int(cols), float(eps),
+                             cur_stream(x)), "rmsnorm");
+  return y;
+}
+
+Tensor swiglu(const Tensor& gu, const c10::optional<Tensor>& out) {
+  need(gu, at::kBFloat16, "gu");
+  TORCH_CHECK(gu.dim() == 2 && gu.size(1) >= 16 && gu.size(1) % 16 == 0, "swiglu: gu must be [M, 2F] with F % 8 == 0");
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(gu.device());
+  const int64_t M = gu.size(0), F = gu.size(1) / 2;
+  Tensor y = out.has_value() ? *out : torch::empty({M, F}, gu.options());
+  need(y, at::kBFloat16, "out");
+  TORCH_CHECK(y.numel() == M * F && y.device() == gu.device(), "swiglu: out has the wrong size");
+  TORCH_CHECK(aligned16(gu) && aligned16(y), "swiglu: tensors must be 16-byte aligned");
+  check(tfsk::swiglu_launch(bf16p(gu), bf16p_mut(y), M, int(F), cur_stream(gu)), "swiglu");
+  return y;
+}
+
 // the (Hf, Wf, ws, shift) of a window_attention grid argument, zeros for None
 struct WattnGrid { int64_t Hf = 0, Wf = 0, ws = 0, shift = 0; };
 WattnGrid wattn_grid(const c10::optional<std::vector<int64_t>>& grid) {
@@ -1490,6 +1586,23 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("causal_attention_supported",
         [](int64_t S, int64_t D) { return tfsk::causal_attention_supported(S, D); }, py::arg("S"), py::arg("D"),
         "whether causal_attention takes length S with heads of width D");
+  m.def("rope_gqa_attention", &rope_gqa_attention, py::arg("qkv"), py::arg("cos"), py::arg("sin"),
+        py::arg("key_adder") = py::none(), py::arg("heads"), py::arg("kv_heads"), py::arg("scale"),
+        py::arg("out") = py::none(),
+        "causal grouped-query attention over packed qkv [B, S, (H + 2*Hkv)*64] (Q | K | V heads): q and k are rotated "
+        "by position with the rotate-half tables cos / sin f32 [S, 32] while they are loaded, query head h reads K / V "
+        "head h / (H / Hkv), H / Hkv in {1, 2, 4, 8}; key_adder an optional f32 [B, S] | [1, S]");
+  m.def("rope_gqa_attention_supported",
+        [](int64_t S, int64_t D, int64_t heads, int64_t kv_heads) {
+          return tfsk::rope_gqa_attention_supported(S, D, heads, kv_heads);
+        }, py::arg("S"), py::arg("D"), py::arg("heads"), py::arg("kv_heads"),
+        "whether rope_gqa_attention takes length S with heads of width D in groups of heads / kv_heads");
+  m.def("rmsnorm", &rmsnorm, py::arg("x"), py::arg("gamma"), py::arg("eps"), py::arg("residual") = py::none(),
+        py::arg("out") = py::none(), py::arg("sum_out") = py::none(),
+        "bf16((x + residual) * rsqrt(mean((x + residual)^2) + eps) * gamma) over the last dim (C % 8 == 0), the row in "
+        "fp32; sum_out, when given, receives bf16(x + residual)");
+  m.def("swiglu", &swiglu, py::arg("gu"), py::arg("out") = py::none(),
+        "bf16(swish(gu[:, :F]) * gu[:, F:]) for gu [M, 2F] bf16, F % 8 == 0");
   m.def("window_attention", &window_attention, py::arg("qkv"), py::arg("bias"), py::arg("mask"), py::arg("heads"),
         py::arg("scale"), py::arg("out") = py::none(), py::arg("grid") = py::none(),
         "windowed attention (Swin): S <= 64 tokens per window, 32-wide heads, per-head bias [H, S, S], optional "
