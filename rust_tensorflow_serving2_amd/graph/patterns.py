@@ -990,7 +990,8 @@ def fuse_causal_attention(g, order, fed, fetch_refs, device, opts):
 
 
 # ------------------------------------------------------------------ Llama: RMSNorm, RoPE + GQA attention, SwiGLU
-ROPE_GROUPS = (1, 2, 4, 8)    # kernels/launch.h rope_gqa_attention_supported
+ROPE_GROUPS = (1, 2, 4, 8)    # kernels/launch.h rope_gqa_attention_supported: heads / kv_heads
+ROPE_HEAD_DIMS = (64, 128)    # ... and head widths (gqattn.hip, gqattn128.hip)
 
 
 class RMSNormOp:
@@ -1050,9 +1051,9 @@ class RopeGQAttentionOp:
     and query head h reading K / V head h / G, G = heads / kv_heads; the mask and
     the adder as in CausalAttentionOp.
 
-    On the device, for D = 64, G in {1, 2, 4, 8} and an adder that is absent or
-    [B | 1, 1, 1, S], one ``rope_gqa_attention`` launch (kernels/gqattn.hip):
-    it rotates in fp32 and rounds to bf16 once, and closes masked keys with
+    On the device, for D in {64, 128}, G in {1, 2, 4, 8} and an adder that is
+    absent or [B | 1, 1, 1, S], one ``rope_gqa_attention`` launch (kernels/gqattn.hip
+    for 64-wide heads, kernels/gqattn128.hip for 128-wide ones): it rotates in fp32 and rounds to bf16 once, and closes masked keys with
     -inf (docs/numerics.md, "RoPE + GQA attention").  Anywhere else the graph's
     own arithmetic with torch, in fp32."""
 
@@ -1072,7 +1073,7 @@ class RopeGQAttentionOp:
         B = qkv.numel() // (S * W)
         key_adder = adder is None or (adder.dim() == 4 and tuple(adder.shape[1:]) == (1, 1, S) and
                                       adder.shape[0] in (1, B))
-        if self.use_hip and qkv.is_cuda and D == 64 and H // K in ROPE_GROUPS and 1 <= S <= MAX_ATTENTION_SEQ and \
+        if self.use_hip and qkv.is_cuda and D in ROPE_HEAD_DIMS and H // K in ROPE_GROUPS and 1 <= S <= MAX_ATTENTION_SEQ and \
                 key_adder:
             from ..ops import hip
             from .fused import _to_bf16

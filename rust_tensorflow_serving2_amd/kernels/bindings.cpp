@@ -1171,7 +1171,7 @@ Tensor rope_gqa_attention(const Tensor& qkv, const Tensor& cos, const Tensor& si
   TORCH_CHECK(heads >= 1 && kv_heads >= 1 && W % (heads + 2 * kv_heads) == 0,
               "rope_gqa_attention: qkv width must be (heads + 2*kv_heads)*head_dim");
   const int64_t D = W / (heads + 2 * kv_heads);
-  TORCH_CHECK(D == 64, "rope_gqa_attention kernel supports head_dim 64, got ", D);
+  TORCH_CHECK(D == 64 || D == 128, "rope_gqa_attention kernel supports head_dim 64 or 128, got ", D);
   TORCH_CHECK(heads % kv_heads == 0 && (heads / kv_heads == 1 || heads / kv_heads == 2 || heads / kv_heads == 4 ||
                                         heads / kv_heads == 8),
               "rope_gqa_attention: heads / kv_heads must be 1, 2, 4 or 8, got ", heads, " / ", kv_heads);

@@ -71,42 +71,19 @@
 #include "common.h"
 #include "gemm_common.h"
 #include "launch.h"
+#include "rope_common.h"
 
 namespace tfsk {
 
 namespace {
 
+using rope::kLog2e;
+using rope::rotate8;
+
 constexpr int D = 64;
 constexpr int KB = 64;                  // keys per block
 constexpr int VT_LD = KB + 8;           // Vt row stride (elements): +16 B pad
 constexpr int HALF = D / 2;             // table row length
-constexpr float kLog2e = 1.4426950408889634f;
-
-__device__ __forceinline__ void unpack_bf16x8(const u32x4& v, float (&f)[8]) {
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    f[2 * e] = __uint_as_float(v[e] << 16);
-    f[2 * e + 1] = __uint_as_float(v[e] & 0xffff0000u);
-  }
-}
-
-// (x1, x2) -> (x1 c - x2 s, x2 c + x1 s) for eight pairs, fp32, one rounding to bf16
-__device__ __forceinline__ void rotate8(u32x4& lo, u32x4& hi, const u32x4 (&c)[2], const u32x4 (&s)[2]) {
-  float x1[8], x2[8], y1[8], y2[8];
-  unpack_bf16x8(lo, x1);
-  unpack_bf16x8(hi, x2);
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    const float ce = __uint_as_float(c[e >> 2][e & 3]), se = __uint_as_float(s[e >> 2][e & 3]);
-    y1[e] = x1[e] * ce - x2[e] * se;
-    y2[e] = x2[e] * ce + x1[e] * se;
-  }
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    lo[e] = gemm::pack_bf16x2(y1[2 * e], y1[2 * e + 1]);
-    hi[e] = gemm::pack_bf16x2(y2[2 * e], y2[2 * e + 1]);
-  }
-}
 
 template <int G>
 __global__ __launch_bounds__(256) void rope_gqa_attention_kernel(const uint16_t* __restrict__ qkv,
@@ -375,7 +352,9 @@ hipError_t launch_gqa(const uint16_t* qkv, const float* cos_t, const float* sin_
 hipError_t rope_gqa_attention_launch(const uint16_t* qkv, const float* cos_t, const float* sin_t,
                                      const float* key_adder, uint16_t* ctx, int B, int S, int H, int Hkv, int Dh,
                                      float scale, long adder_bstride, hipStream_t st) {
-  if (!rope_gqa_attention_supported(S, Dh, H, Hkv) || B < 0 || qkv == nullptr || ctx == nullptr ||
+  if (Dh == 128)                                 // 128-wide heads: gqattn128.hip
+    return rope_gqa_attention128_launch(qkv, cos_t, sin_t, key_adder, ctx, B, S, H, Hkv, scale, adder_bstride, st);
+  if (Dh != D || !rope_gqa_attention_supported(S, Dh, H, Hkv) || B < 0 || qkv == nullptr || ctx == nullptr ||
       cos_t == nullptr || sin_t == nullptr)
     return hipErrorInvalidValue;
   if (adder_bstride != 0 && adder_bstride != S) return hipErrorInvalidValue;

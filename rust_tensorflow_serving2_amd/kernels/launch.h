@@ -357,21 +357,26 @@ constexpr bool causal_attention_supported(int64_t S, int64_t D) { return D == 64
 hipError_t causal_attention_launch(const uint16_t* qkv, const float* key_adder, uint16_t* ctx, int B, int S, int H,
                                    int D, float scale, long adder_bstride, hipStream_t stream, int qb = 0);
 
-// Causal grouped-query attention with rotary embedding at load (kernels/gqattn.hip):
-// qkv [B][S][(H + 2*Hkv)*64] bf16 (Q heads | K heads | V heads), cos / sin f32 [S][32]
-// (one half of the rotate-half tables); q and k are rotated by their position in
-// fp32 and rounded to bf16 once, query head h reads K / V head h / (H / Hkv), then
+// Causal grouped-query attention with rotary embedding at load (kernels/gqattn.hip for
+// D = 64, kernels/gqattn128.hip for D = 128): qkv [B][S][(H + 2*Hkv)*D] bf16 (Q heads |
+// K heads | V heads), cos / sin f32 [S][D / 2] (one half of the rotate-half tables, the
+// pairs are dims (i, i + D / 2)); q and k are rotated by their position in fp32 and
+// rounded to bf16 once, query head h reads K / V head h / (H / Hkv), then
 // ctx[b,q,h,:] = softmax over key <= q of (q~ k~^T * scale + key_adder) V as in
-// causal_attention_launch.  D = 64, 1 <= S <= kMaxAttentionSeq, H % Hkv == 0 with
+// causal_attention_launch.  D in {64, 128}, 1 <= S <= kMaxAttentionSeq, H % Hkv == 0 with
 // H / Hkv in {1, 2, 4, 8}; qkv, ctx and the tables 16-B aligned, one image's qkv
 // rows below 2 GiB.  Anything else is hipErrorInvalidValue and launches nothing.
 constexpr bool rope_gqa_attention_supported(int64_t S, int64_t D, int64_t H, int64_t Hkv) {
-  return D == 64 && S >= 1 && S <= kMaxAttentionSeq && Hkv >= 1 && H >= Hkv && H % Hkv == 0 &&
+  return (D == 64 || D == 128) && S >= 1 && S <= kMaxAttentionSeq && Hkv >= 1 && H >= Hkv && H % Hkv == 0 &&
          (H / Hkv == 1 || H / Hkv == 2 || H / Hkv == 4 || H / Hkv == 8);
 }
 hipError_t rope_gqa_attention_launch(const uint16_t* qkv, const float* cos_t, const float* sin_t,
                                      const float* key_adder, uint16_t* ctx, int B, int S, int H, int Hkv, int D,
                                      float scale, long adder_bstride, hipStream_t stream);
+// the D = 128 kernels; rope_gqa_attention_launch dispatches here
+hipError_t rope_gqa_attention128_launch(const uint16_t* qkv, const float* cos_t, const float* sin_t,
+                                        const float* key_adder, uint16_t* ctx, int B, int S, int H, int Hkv,
+                                        float scale, long adder_bstride, hipStream_t stream);
 
 // RMSNorm over the last dim (kernels/llama.hip): y = bf16((x + r) * rsqrt(mean((x + r)^2) + eps) * gamma),
 // the row kept in fp32; r an optional residual (null: none), sum an optional second output bf16(x + r)

@@ -26,7 +26,8 @@ sequence length.
   + ``Squeeze``) times the untied ``lm_head`` -> ``logits`` ``[-1, vocab]``.
 
 Signature ``serving_default`` (predict): inputs ``input_ids``, ``input_mask``
-(int32 [-1, S]); outputs ``logits`` and ``hidden``.  Heads are 64 wide.
+(int32 [-1, S]); outputs ``logits`` and ``hidden``.  Heads are ``head_dim`` wide: 64
+(written so above) unless the config or the argument says 128.
 """
 from __future__ import annotations
 
@@ -58,8 +59,11 @@ MASK_FILL = 1e4
 QKV_GAIN = 2.0
 RESIDUAL_GAIN = 0.0025
 EMBED_STD = 0.1
-# name -> (hidden, layers, heads, kv_heads, mlp, seq_len, vocab)
-CONFIGS = {"llama_1b": (2048, 16, 32, 8, 8192, 1024, 32000), "llama_tiny": (256, 2, 4, 2, 512, 160, 503)}
+# name -> (hidden, layers, heads, kv_heads, mlp, seq_len, vocab[, head_dim = HEAD_DIM]).  llama_8b is
+# Llama-3-8B's decoder with the vocabulary cut to 32000, which keeps the export and the head small.
+CONFIGS = {"llama_1b": (2048, 16, 32, 8, 8192, 1024, 32000), "llama_tiny": (256, 2, 4, 2, 512, 160, 503),
+           "llama_tiny_d128": (512, 2, 4, 2, 1024, 160, 503, 128),
+           "llama_8b": (4096, 32, 32, 8, 14336, 1024, 32000, 128)}
 
 
 def rope_tables(S: int, theta: float = ROPE_THETA, dim: int = HEAD_DIM):
@@ -87,17 +91,17 @@ def rms_norm(g, x, dim, rng, eps, name):
         return g.node("Mul", "mul_1", [g.node("Mul", "mul", [x, rs], T=F32), gamma], T=F32)
 
 
-def _heads(g, x, S, nH, nKV, name, tile_axis=3):
-    """[B * S, nKV * 64] -> [B, nH, S, 64]; each of the nKV heads repeated nH / nKV times."""
+def _heads(g, x, S, nH, nKV, name, tile_axis=3, head_dim=HEAD_DIM):
+    """[B * S, nKV * head_dim] -> [B, nH, S, head_dim]; each of the nKV heads repeated nH / nKV times."""
     if nH != nKV:
         mult = [1, 1, 1, 1, 1]
         mult[tile_axis] = nH // nKV
         x = g.node("Reshape", f"Reshape_{name}_kv", [x, g.const(f"Reshape_{name}_kv/shape",
-                                                               np.array([-1, S, nKV, 1, HEAD_DIM], np.int32))], T=F32)
+                                                               np.array([-1, S, nKV, 1, head_dim], np.int32))], T=F32)
         x = g.node("Tile", f"Tile_{name}", [x, g.const(f"Tile_{name}/multiples", np.array(mult, np.int32))], T=F32,
                    Tmultiples=I32)
     x = g.node("Reshape", f"Reshape_{name}", [x, g.const(f"Reshape_{name}/shape",
-                                                        np.array([-1, S, nH, HEAD_DIM], np.int32))], T=F32)
+                                                        np.array([-1, S, nH, head_dim], np.int32))], T=F32)
     return g.node("Transpose", f"transpose_{name}", [x, g.const(f"transpose_{name}/perm",
                                                                 np.array([0, 2, 1, 3], np.int32))], T=F32, Tperm=I32)
 
@@ -112,22 +116,23 @@ def rotate(g, x, cos, sin, name):
                                            g.node("Mul", f"mul_{name}_sin", [rot, sin], T=F32)], T=F32)
 
 
-def attention_core(g, x, C, S, nH, nKV, rng, adder, tables, rotate_v=False, tile_axis=3, const_weights=False):
-    """q / k / v denses on x [B * S, C] -> the context [B * S, nH * 64] (before o_proj).  ``tables`` =
+def attention_core(g, x, C, S, nH, nKV, rng, adder, tables, rotate_v=False, tile_axis=3, const_weights=False,
+                   head_dim=HEAD_DIM):
+    """q / k / v denses on x [B * S, C] -> the context [B * S, nH * head_dim] (before o_proj).  ``tables`` =
     (cos, sin) arrays; ``rotate_v`` and ``tile_axis`` spell graphs that are NOT Llama's attention;
     ``const_weights`` writes the kernels as constants (a graph that needs no checkpoint)."""
     std = math.sqrt(QKV_GAIN / C)
-    q = linear(g, x, C, nH * HEAD_DIM, rng, "q_proj", std, const_weights)
-    k = linear(g, x, C, nKV * HEAD_DIM, rng, "k_proj", std, const_weights)
-    v = linear(g, x, C, nKV * HEAD_DIM, rng, "v_proj", std, const_weights)
+    q = linear(g, x, C, nH * head_dim, rng, "q_proj", std, const_weights)
+    k = linear(g, x, C, nKV * head_dim, rng, "k_proj", std, const_weights)
+    v = linear(g, x, C, nKV * head_dim, rng, "v_proj", std, const_weights)
     cos, sin = g.const("rope_cos", tables[0]), g.const("rope_sin", tables[1])
-    q = rotate(g, _heads(g, q, S, nH, nH, "query"), cos, sin, "query")
-    k = rotate(g, _heads(g, k, S, nH, nKV, "key", tile_axis), cos, sin, "key")
-    v = _heads(g, v, S, nH, nKV, "value", tile_axis)
+    q = rotate(g, _heads(g, q, S, nH, nH, "query", head_dim=head_dim), cos, sin, "query")
+    k = rotate(g, _heads(g, k, S, nH, nKV, "key", tile_axis, head_dim), cos, sin, "key")
+    v = _heads(g, v, S, nH, nKV, "value", tile_axis, head_dim)
     if rotate_v:
         v = rotate(g, v, cos, sin, "value")
     w = g.node("BatchMatMulV2", "MatMul", [q, k], T=F32, adj_x=False, adj_y=True)
-    w = g.node("Mul", "mul", [w, _c(g, "mul/y", 1.0 / math.sqrt(HEAD_DIM))], T=F32)
+    w = g.node("Mul", "mul", [w, _c(g, "mul/y", 1.0 / math.sqrt(head_dim))], T=F32)
     b = g.const("band", np.tril(np.ones((1, 1, S, S), np.float32)))
     one_minus = g.node("Sub", "sub", [_c(g, "sub/x", 1.0), b], T=F32)
     fill = g.node("Mul", "mul_2", [_c(g, "mul_2/x", MASK_FILL), one_minus], T=F32)
@@ -138,7 +143,7 @@ def attention_core(g, x, C, S, nH, nKV, rng, adder, tables, rotate_v=False, tile
     a = g.node("BatchMatMulV2", "MatMul_1", [p, v], T=F32, adj_x=False, adj_y=False)
     a = g.node("Transpose", "transpose_out", [a, g.const("transpose_out/perm", np.array([0, 2, 1, 3], np.int32))],
                T=F32, Tperm=I32)
-    return g.node("Reshape", "Reshape_out", [a, g.const("Reshape_out/shape", np.array([-1, nH * HEAD_DIM], np.int32))],
+    return g.node("Reshape", "Reshape_out", [a, g.const("Reshape_out/shape", np.array([-1, nH * head_dim], np.int32))],
                   T=F32)
 
 
@@ -150,15 +155,16 @@ def swiglu_mlp(g, x, C, F, rng):
 
 
 def build_graph(config: str = "llama_1b", seed: int = 0, layers: int = None, hidden: int = None, heads: int = None,
-                kv_heads: int = None, mlp: int = None, seq_len: int = None, vocab: int = None):
+                kv_heads: int = None, mlp: int = None, seq_len: int = None, vocab: int = None, head_dim: int = None):
     if config not in CONFIGS:
         raise ValueError(f"unknown Llama config {config!r}: one of {sorted(CONFIGS)}")
-    c_hidden, c_layers, c_heads, c_kv, c_mlp, c_seq, c_vocab = CONFIGS[config]
+    c_hidden, c_layers, c_heads, c_kv, c_mlp, c_seq, c_vocab = CONFIGS[config][:7]
+    D = head_dim or (CONFIGS[config][7:] or (HEAD_DIM,))[0]
     C, L, nH = hidden or c_hidden, c_layers if layers is None else layers, heads or c_heads
     nKV, F, S, V = kv_heads or c_kv, mlp or c_mlp, seq_len or c_seq, vocab or c_vocab
-    if C != nH * HEAD_DIM or nH % nKV:
-        raise ValueError(f"hidden {C} is not heads {nH} x {HEAD_DIM}, or kv_heads {nKV} does not divide heads")
-    tables = rope_tables(S)
+    if C != nH * D or nH % nKV:
+        raise ValueError(f"hidden {C} is not heads {nH} x {D}, or kv_heads {nKV} does not divide heads")
+    tables = rope_tables(S, dim=D)
     g = GraphBuilder()
     rng = np.random.default_rng(seed)
     ids = g.placeholder("input_ids", T.DT_INT32, [-1, S])
@@ -176,7 +182,7 @@ def build_graph(config: str = "llama_1b", seed: int = 0, layers: int = None, hid
             with g.scope(f"layers_{li}"):
                 with g.scope("self_attn"):
                     h = rms_norm(g, x, C, rng, RMS_EPS, "input_layernorm")
-                    h = attention_core(g, h, C, S, nH, nKV, rng, adder, tables)
+                    h = attention_core(g, h, C, S, nH, nKV, rng, adder, tables, head_dim=D)
                     h = linear(g, h, C, C, rng, "o_proj", math.sqrt(RESIDUAL_GAIN / C))
                     x = g.node("AddV2", "add_residual", [x, h], T=F32)
                 with g.scope("mlp"):

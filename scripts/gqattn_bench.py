@@ -13,7 +13,15 @@ rounds, as a share of the median), which is what a ratio has to beat.  The
 composition is timed whole and its attention launch alone ("cattn only": what the
 composition would cost if the rotation and the repeat were free).
 
-    python scripts/gqattn_bench.py [--shapes B,S,H,Hkv ...] [--reps 21] [--rounds 5] [--json]
+A shape with a fifth field D = 128 runs kernels/gqattn128.hip.  causal_attention
+has no 128-wide form, so there the baselines are (a) "op torch path": what the
+graph op ran before the kernel existed, RopeGQAttentionOp with use_hip = False on
+the device (fp32, K / V repeated, [B, H, S, S] scores materialised), and (b)
+"torch sdpa": the rotation in fp32 rounded to bf16, then
+torch.nn.functional.scaled_dot_product_attention(is_causal=True) over K / V
+repeated for their groups.  ``--d128`` runs the D = 128 shape list.
+
+    python scripts/gqattn_bench.py [--shapes B,S,H,Hkv[,D] ...] [--d128] [--reps 21] [--rounds 5] [--json]
 """
 import argparse
 import json
@@ -27,6 +35,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from dwconv_bench import timed  # noqa: E402
 
 SHAPES = [(b, s, 32, k) for k in (8, 4) for s in (128, 512, 1024, 2048) for b in (1, 8)]
+SHAPES_D128 = [(b, s, 32, k, 128) for k in (8, 32) for s in (128, 512, 1024, 2048) for b in (1, 8)]
 
 
 def parse(text):
@@ -48,9 +57,49 @@ def compose(qkv, cos, sin, h, k):
     return torch.cat([rot(q, h), kr, vr], 2).reshape(b, s, 3 * h * 64)
 
 
+def rotated(t, n, d, cos, sin):
+    """[B, S, n d] -> [B, S, n, d]: rotate-half in fp32, one rounding to bf16."""
+    b, s, _ = t.shape
+    t = t.reshape(b, s, n, d).float()
+    t1, t2 = t[..., :d // 2], t[..., d // 2:]
+    c, sn = cos[None, :, None, :], sin[None, :, None, :]
+    return torch.cat([t1 * c - t2 * sn, t2 * c + t1 * sn], -1).to(torch.bfloat16)
+
+
+def sdpa(qkv, cos, sin, h, k, d, scale, out):
+    """Baseline (b): torch rotation, K / V repeated, torch's fused causal attention."""
+    b, s, _ = qkv.shape
+    q, kk, v = qkv.split([h * d, k * d, k * d], -1)
+    q = rotated(q, h, d, cos, sin).transpose(1, 2)
+    kk = rotated(kk, k, d, cos, sin).repeat_interleave(h // k, 2).transpose(1, 2)
+    v = v.reshape(b, s, k, d).repeat_interleave(h // k, 2).transpose(1, 2)
+    y = torch.nn.functional.scaled_dot_product_attention(q, kk, v, is_causal=True, scale=scale)
+    out.copy_(y.transpose(1, 2).reshape(b, s, h * d))
+
+
+def candidates(H, qkv, cos, sin, h, k, d, out):
+    """name -> callable writing out[name]; the first is the kernel, the second what it is checked against."""
+    scale = d ** -0.5
+    runs = {"rope_gqa": lambda: H.rope_gqa_attention(qkv, cos, sin, None, h, k, scale, out["rope_gqa"])}
+    if d == 64:
+        packed = compose(qkv, cos, sin, h, k)
+        runs["composition"] = lambda: H.causal_attention(compose(qkv, cos, sin, h, k), None, h, scale,
+                                                         out["composition"])
+        runs["cattn only"] = lambda: H.causal_attention(packed, None, h, scale, out["cattn only"])
+    else:
+        from rust_tensorflow_serving2_amd.graph.patterns import RopeGQAttentionOp
+        b, s, _ = qkv.shape
+        op = RopeGQAttentionOp(h, k, d, s, scale, -10000.0, cos, sin, qkv.device, False)
+        flat = qkv.reshape(b * s, -1)
+        runs["op torch path"] = lambda: out["op torch path"].copy_(op(None, None, [flat])[0].reshape(b, s, h * d))
+        runs["torch sdpa"] = lambda: sdpa(qkv, cos, sin, h, k, d, scale, out["torch sdpa"])
+    return runs
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--shapes", nargs="+", type=parse, default=SHAPES, metavar="B,S,H,Hkv")
+    ap.add_argument("--shapes", nargs="+", type=parse, default=None, metavar="B,S,H,Hkv[,D]")
+    ap.add_argument("--d128", action="store_true", help="the D = 128 shape list instead of the D = 64 one")
     ap.add_argument("--reps", type=int, default=21)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--json", action="store_true")
@@ -62,32 +111,29 @@ def main():
     H = ops.hip()
     dev = torch.device("cuda:0")
     flush = ops._flush_buffer()
-    names = ["rope_gqa", "composition", "cattn only"]
-    print(f"{'B x S x H/Hkv':>16} " + " ".join(f"{n + ' us':>15} {'spread':>6}" for n in names) +
-          f" {'composition / rope_gqa':>23}")
-    for b, s, h, k in args.shapes:
+    for shape in args.shapes or (SHAPES_D128 if args.d128 else SHAPES):
+        b, s, h, k = shape[:4]
+        d = shape[4] if len(shape) > 4 else 64
         g = torch.Generator().manual_seed(s * 100 + b)
-        qkv = torch.randn(b, s, (h + 2 * k) * 64, generator=g).to(torch.bfloat16).to(dev)
-        cos, sin = (torch.from_numpy(t[0, 0, :, :32].copy()).to(dev) for t in llama.rope_tables(s))
-        out = {n: torch.empty(b, s, h * 64, dtype=torch.bfloat16, device=dev) for n in names}
-        packed = compose(qkv, cos, sin, h, k)
-        runs = {"rope_gqa": lambda: H.rope_gqa_attention(qkv, cos, sin, None, h, k, 0.125, out["rope_gqa"]),
-                "composition": lambda: H.causal_attention(compose(qkv, cos, sin, h, k), None, h, 0.125,
-                                                          out["composition"]),
-                "cattn only": lambda: H.causal_attention(packed, None, h, 0.125, out["cattn only"])}
+        qkv = torch.randn(b, s, (h + 2 * k) * d, generator=g).to(torch.bfloat16).to(dev)
+        cos, sin = (torch.from_numpy(t[0, 0, :, :d // 2].copy()).to(dev) for t in llama.rope_tables(s, dim=d))
+        names = ["rope_gqa", "composition", "cattn only"] if d == 64 else ["rope_gqa", "op torch path", "torch sdpa"]
+        out = {n: torch.empty(b, s, h * d, dtype=torch.bfloat16, device=dev) for n in names}
+        runs = candidates(H, qkv, cos, sin, h, k, d, out)
         rounds = {n: [] for n in runs}
         for _ in range(args.rounds):
             for n, fn in runs.items():                       # alternating: every round times every candidate once
                 rounds[n].append(timed(fn, flush, args.reps))
-        # the same roundings in the same order: the two paths agree to the last bit or nearly
-        err = (out["rope_gqa"].float() - out["composition"].float()).abs().max().item()
+        # the same roundings in the same order (D = 64) or an fp32 computation of the same thing (D = 128)
+        err = (out["rope_gqa"].float() - out[names[1]].float()).abs().max().item()
         assert err < 0.05, err
         med = {n: statistics.median(v) for n, v in rounds.items()}
         spread = {n: (max(v) - min(v)) / med[n] for n, v in rounds.items()}
-        cells = " ".join(f"{med[n]:15.1f} {spread[n]:6.1%}" for n in names)
-        print(f"{f'{b}x{s}x{h}/{k}':>16} {cells} {med['composition'] / med['rope_gqa']:23.2f}", flush=True)
+        cells = " ".join(f"{n} {med[n]:.1f} us (spread {spread[n]:.1%})" for n in names)
+        ratios = " ".join(f"{n} / rope_gqa {med[n] / med['rope_gqa']:.2f}" for n in names[1:])
+        print(f"{f'{b}x{s}x{h}/{k} D={d}':>22}  {cells}  {ratios}", flush=True)
         if args.json:
-            print(json.dumps({"b": b, "s": s, "h": h, "hkv": k, "rounds": args.rounds,
+            print(json.dumps({"b": b, "s": s, "h": h, "hkv": k, "d": d, "rounds": args.rounds,
                               "us": {n: [round(x, 2) for x in v] for n, v in rounds.items()}}), flush=True)
 
 

@@ -5,7 +5,7 @@ The reference downloads ``resnet_v2_fp32_savedmodel_NHWC`` and copies version
 Offline, we write random-init SavedModels of the same architectures in the
 same ``<root>/<name>/<version>/`` layout:
 
-    python serving/make_models.py --root serving/models [--models resnet,resnet_v2,resnext50,mobilenet,mobilenet_v2,mobilenet_v3_large,mobilenet_v3_small,efficientnet_b0,convnext_tiny,vit_b16,swin_tiny,bert,gpt2,gpt2_tiny,llama,llama_tiny,dlrm,half_plus_two]
+    python serving/make_models.py --root serving/models [--models resnet,resnet_v2,resnext50,mobilenet,mobilenet_v2,mobilenet_v3_large,mobilenet_v3_small,efficientnet_b0,convnext_tiny,vit_b16,swin_tiny,bert,gpt2,gpt2_tiny,llama,llama_tiny,llama_8b,llama_tiny_d128,dlrm,half_plus_two]
 
 * ``resnet``        ResNet-50 v1.5 (NHWC, alias "input", outputs classes/probabilities)
 * ``resnet_v2``     ResNet-50 v2 pre-activation (the fetch.sh model's architecture)
@@ -23,6 +23,8 @@ same ``<root>/<name>/<version>/`` layout:
 * ``llama`` (= ``llama_1b``) / ``llama_tiny``  Llama-style decoder, 2048 wide, 16 layers, 32 query heads over 8 K/V heads, SwiGLU 8192,
                     S = 1024 (RMSNorm, rotate-half RoPE tables as constants, K / V repeated by Tile, untied head on the
                     last position; input_ids / input_mask) and a 2-layer, 256-wide one (4 / 2 heads) at S = 160
+* ``llama_8b`` / ``llama_tiny_d128``  the same decoder with 128-wide heads: 4096 wide, 32 layers, 32 / 8 heads, SwiGLU 14336,
+                    S = 1024, vocabulary 32000 (~13 GB of fp32 weights), and a 2-layer, 512-wide one (4 / 2 heads) at S = 160
 * ``dlrm``          DLRM, Criteo layout (13 dense + 26 sparse features, D = 128, tables capped at 40000 rows: 198 MB;
                     Predict dense / sparse, Classify and Regress over tf.Examples)
 * ``half_plus_two`` TF Serving's canonical test model
@@ -78,7 +80,7 @@ def main(argv=None):
         elif m in ("gpt2", "gpt2_tiny"):
             from rust_tensorflow_serving2_amd.models import gpt2
             gpt2.export(out, m, seed=args.seed)
-        elif m in ("llama", "llama_1b", "llama_tiny"):
+        elif m in ("llama", "llama_1b", "llama_tiny", "llama_8b", "llama_tiny_d128"):
             from rust_tensorflow_serving2_amd.models import llama
             llama.export(out, "llama_1b" if m == "llama" else m, seed=args.seed)
         elif m == "dlrm":
