@@ -23,6 +23,11 @@
   and ``swish(x Wg) * (x Wu)``
         => _RMSNorm(x [, residual])   _FusedQKV(x) -> _RopeGQAttention(qkv, key_adder)   _FusedMatMul -> _SwiGLU
 
+* ModernBERT's block (``fuse_rope_encoder_attention``, ``fuse_geglu``): the bidirectional core with q and k rotated by
+  position and an optional constant local band ``fill * (|i - j| > w)`` added to the scores, and
+  ``gelu_erf(s0) * s1`` over the two halves of one dense
+        => _FusedQKV(x) -> _RopeAttention(qkv, key_adder; window)   _FusedMatMul -> _GeGLU
+
 * Swin's windowed attention (``fuse_window_attention``) and the roll / partition /
   reverse layout around it (``fold_window_layout``)
         => _FusedQKV(x)  ->  _WindowAttention(qkv; bias, mask, grid)
@@ -1315,6 +1320,267 @@ def fuse_swiglu(g, order, fed, fetch_refs, device, opts):
         c.refresh()
 
 
+# ------------------------------------------------------------------ ModernBERT: RoPE encoder attention, GeGLU
+class RopeAttentionOp:
+    """Bidirectional attention over a packed [Q heads | K heads | V heads] buffer with q
+    and k rotated by position (rotate-half, tables ``cos`` / ``sin`` [S, D / 2]).  Key j
+    is open for query i iff ``|i - j| <= window``; ``window`` -1 opens every key.
+
+    On the device, for D = 64, S within range and an adder that is absent or
+    [B | 1, 1, 1, S], one ``rope_attention`` launch (kernels/rattn.hip): it rotates in
+    fp32 and rounds to bf16 once, and closes the keys outside the window with -inf
+    (docs/numerics.md, "RoPE encoder attention").  Anywhere else the graph's own
+    arithmetic with torch, in fp32: the matched ``fill`` added outside the window."""
+
+    def __init__(self, heads, head_dim, seq, scale, window, fill, cos, sin, device, use_hip):
+        self.h, self.d, self.s = heads, head_dim, seq
+        self.scale, self.window, self.fill, self.use_hip = scale, window, fill, use_hip
+        self.cos = to_device(cos.float().contiguous(), device)
+        self.sin = to_device(sin.float().contiguous(), device)
+
+    def __call__(self, ctx, node, ins):
+        qkv = O.to_torch(ins[0])
+        adder = O.to_torch(ins[1]) if len(ins) > 1 else None
+        S, H, D = self.s, self.h, self.d
+        W = 3 * H * D
+        if qkv.numel() % (S * W):
+            raise O.OpError(f"{node.name}: {list(qkv.shape)} is not [B * {S}, {W}]")
+        B = qkv.numel() // (S * W)
+        key_adder = adder is None or (adder.dim() == 4 and tuple(adder.shape[1:]) == (1, 1, S) and
+                                      adder.shape[0] in (1, B))
+        if self.use_hip and qkv.is_cuda and D == 64 and 1 <= S <= MAX_ATTENTION_SEQ and key_adder:
+            from ..ops import hip
+            from .fused import _to_bf16
+            q3 = _to_bf16(qkv).reshape(B, S, W).contiguous()
+            ka = None if adder is None else adder.float().reshape(-1, S).contiguous().to(qkv.device)
+            y = hip().rope_attention(q3, self.cos, self.sin, ka, H, self.scale, self.window)
+            return [y.reshape(B * S, H * D)]
+        f = qkv.float().reshape(B, S, 3, H, D).permute(2, 0, 3, 1, 4)
+        cos = torch.cat([self.cos, self.cos], -1).to(f.device)
+        sin = torch.cat([self.sin, self.sin], -1).to(f.device)
+
+        def rot(t):
+            return t * cos + torch.cat([-t[..., D // 2:], t[..., :D // 2]], -1) * sin
+        sc = rot(f[0]) @ rot(f[1]).transpose(-1, -2) * self.scale
+        if self.window >= 0:
+            pos = torch.arange(S, device=sc.device)
+            sc = sc + self.fill * ((pos[:, None] - pos[None, :]).abs() > self.window).float()
+        if adder is not None:
+            sc = sc + adder.float().to(sc.device)
+        y = (torch.softmax(sc, -1) @ f[2]).permute(0, 2, 1, 3).reshape(B * S, H * D)
+        return [y if not qkv.is_cuda else y.to(qkv.dtype)]
+
+
+class GeGLUOp:
+    """gelu_erf(gu[:, :F]) * gu[:, F:] after one GEMM over [W_gate | W_up]: ``geglu``
+    (kernels/llama.hip) on the device for F % 8 == 0, else torch in fp32."""
+
+    def __init__(self, width: int, use_hip: bool):
+        self.f, self.use_hip = width, use_hip
+
+    def __call__(self, ctx, node, ins):
+        gu = O.to_torch(ins[0])
+        F_ = self.f
+        if gu.shape[-1] != 2 * F_:
+            raise O.OpError(f"{node.name}: {list(gu.shape)} is not [M, {2 * F_}]")
+        if self.use_hip and gu.is_cuda and F_ % 8 == 0:
+            from ..ops import hip
+            from .fused import _to_bf16
+            y = hip().geglu(_to_bf16(gu).reshape(-1, 2 * F_).contiguous())
+            return [y.reshape(list(gu.shape[:-1]) + [F_])]
+        gf = gu.float()
+        y = F.gelu(gf[..., :F_]) * gf[..., F_:]
+        return [y if not gu.is_cuda else y.to(gu.dtype)]
+
+
+def _reaches_qk(g, ref) -> bool:
+    """Whether ref is q k^T (BatchMatMul, adj_y) under an optional scale and any number of adds."""
+    n = _node(g, ref)
+    if n is None:
+        return False
+    if n.op in ("Add", "AddV2") and len(n.inputs) == 2:
+        return _reaches_qk(g, n.inputs[0]) or _reaches_qk(g, n.inputs[1])
+    if n.op in ("Mul", "RealDiv"):
+        sv = _scale_of(g, n)
+        n = _node(g, sv[1]) if sv is not None else None
+    return n is not None and n.op in _BMM and not n.attr("adj_x", False) and bool(n.attr("adj_y", False))
+
+
+def _window_of(band: torch.Tensor, S: int):
+    """band = fill * (|i - j| > w) as [S, S] under leading 1s, w >= 0 an integer and
+    fill <= -MIN_CAUSAL_FILL -> (w, fill), else None.  w comes from row 0, then the whole matrix is compared.
+    A band that closes nothing in row 0 (all zeros, or w >= S - 1) has no fill to read and is None too: such a
+    graph stays unfused rather than being taken for the global form."""
+    b = _square(band)
+    if b is None or b.shape[0] != S or not b.is_floating_point():
+        return None
+    closed = torch.nonzero(b[0]).reshape(-1)
+    if closed.numel() == 0 or int(closed[0]) == 0:
+        return None                   # nothing closed in row 0: no fill to read; key 0 closed for query 0: no window
+    w, fill = int(closed[0]) - 1, float(b[0, int(closed[0])])
+    if not fill <= -MIN_CAUSAL_FILL:
+        return None
+    pos = torch.arange(S)
+    want = torch.where((pos[:, None] - pos[None, :]).abs() > w, fill, 0.0).double()
+    return (w, fill) if torch.equal(b.double().cpu(), want) else None
+
+
+def fuse_rope_encoder_attention(g, order, fed, fetch_refs, device, opts):
+    """ModernBERT's attention core -> _FusedQKV -> _RopeAttention: fuse_attention's skeleton::
+
+        w = BatchMatMul(q, k, adj_y)  [Mul by c | RealDiv by c: _scale_of]
+        scores = w [+ band] [+ adder]                     (AddV2, operands and the two adds in either order)
+        y = Reshape(Transpose(BatchMatMul(Softmax(scores), v), [0, 2, 1, 3]), [-1, H * D])
+
+    with q and k each rotated by position (``_rope_of``) with equal tables of the
+    pattern's S and v not; q, k, v from three denses on one input, each H * D wide, or
+    from one packed dense through Split / SplitV (``_split_qkv``); at most one
+    non-constant ``adder`` (the op takes [B | 1, 1, 1, S] on the device) and at most
+    one constant ``band``, which must be exactly ``fill * (|i - j| > w)`` (``_window_of``).
+    window = w, or -1 without a band.
+
+    Runs after fuse_rope_attention and takes nothing it takes: that pass needs a
+    Sub or SelectV2 mask under the Softmax, this one only adds, and a causal band
+    spelled as an adder is not symmetric.  A band with a hole, an asymmetric
+    band, a weaker fill, a band that closes nothing in row 0, a per-head constant, tables that differ between q and k or are of
+    another S, a rotated v, or an interior node read elsewhere leaves the graph
+    alone."""
+    from .fused import FusedMatMul, _Ctx
+    c = _Ctx(g, order, fed, fetch_refs, device, opts)
+    for name in list(order):
+        out = g.nodes.get(name)
+        if out is None or out.op != "Reshape":
+            continue
+        t2 = _node(g, out.inputs[0])
+        if t2 is None or t2.op != "Transpose" or _ints(g, t2.inputs[1]) != [0, 2, 1, 3]:
+            continue
+        pv = _node(g, t2.inputs[0])
+        if pv is None or pv.op not in _BMM or pv.attr("adj_x", False) or pv.attr("adj_y", False):
+            continue
+        sm = _node(g, pv.inputs[0])
+        if sm is None or sm.op != "Softmax":
+            continue
+        interior = [t2, pv, sm]
+        # ---- the adds under the Softmax: at most one constant (the band) and one other (the adder)
+        cur, band, adder_ref, ok = _node(g, sm.inputs[0]), None, None, True
+        while ok and cur is not None and cur.op in ("Add", "AddV2") and len(cur.inputs) == 2:
+            sides = [k for k in (0, 1) if _reaches_qk(g, cur.inputs[k])]
+            if len(sides) != 1:
+                ok = False
+                break
+            other = cur.inputs[1 - sides[0]]
+            cv = _const_t(g, other)
+            if cv is not None and band is None:
+                band = cv
+            elif cv is None and adder_ref is None:
+                adder_ref = other
+            else:
+                ok = False
+            interior.append(cur)
+            cur = _node(g, cur.inputs[sides[0]])
+        if not ok:
+            continue
+        scale = 1.0
+        sv = _scale_of(g, cur) if cur is not None and cur.op in ("Mul", "RealDiv") else None
+        if sv is not None:
+            scale = sv[0]
+            interior.append(cur)
+            cur = _node(g, sv[1])
+        qk = cur
+        if qk is None or qk.op not in _BMM or qk.attr("adj_x", False) or not qk.attr("adj_y", False):
+            continue
+        interior.append(qk)
+        rq, rk = _rope_of(g, qk.inputs[0]), _rope_of(g, qk.inputs[1])
+        if rq is None or rk is None or not torch.equal(rq[1], rk[1]) or not torch.equal(rq[2], rk[2]):
+            continue
+        hq, hk, hv = _heads_of(g, c, rq[0]), _heads_of(g, c, rk[0]), _heads_of(g, c, pv.inputs[1])
+        if hq is None or hk is None or hv is None or hq[1:4] != hk[1:4] or hq[1:4] != hv[1:4]:
+            continue
+        S, H, D = hq[1:4]
+        if tuple(rq[1].shape) != (S, D // 2) or _ints(g, out.inputs[1]) != [-1, H * D]:
+            continue
+        window, fill = -1, 0.0
+        if band is not None:
+            wf = _window_of(band, S)
+            if wf is None:
+                continue
+            window, fill = wf
+        interior += rq[3] + rk[3] + hq[4] + hk[4] + hv[4]
+        if adder_ref is not None and adder_ref[0] in {n.name for n in interior}:
+            continue
+        packed = _split_qkv(g, c, [hq[0], hk[0], hv[0]], H, D)
+        if packed is not None:
+            x_ref, w, b, qkv_nodes = packed
+        else:
+            dq, dk, dv = _dense_src(g, c, hq[0]), _dense_src(g, c, hk[0]), _dense_src(g, c, hv[0])
+            if not (dq and dk and dv and dq[0] == dk[0] == dv[0]) or any(d[1].shape[1] != H * D for d in (dq, dk, dv)):
+                continue
+            x_ref = dq[0]
+            w, b = torch.cat([dq[1], dk[1], dv[1]], dim=1), torch.cat([dq[2], dk[2], dv[2]])
+            qkv_nodes = dq[3] + dk[3] + dv[3]
+        if not _interior_ok(c, interior + qkv_nodes, out):
+            continue
+        qkv_name = g.unique_name(out.name + "/fused_qkv")
+        g.add(Node(name=qkv_name, op="_FusedQKV", inputs=[x_ref],
+                   attrs={"_impl": FusedMatMul(w, b, "none", False, device, c.use_hip, qkv_name)}))
+        _remove(g, interior + qkv_nodes)
+        out.op = "_RopeAttention"
+        out.inputs = [(qkv_name, 0)] + ([adder_ref] if adder_ref is not None else [])
+        out.ctrl = []
+        out.attrs = {"_impl": RopeAttentionOp(H, D, S, scale, window, fill, rq[1], rq[2], device, c.use_hip)}
+        c.refresh()
+
+
+def fuse_geglu(g, order, fed, fetch_refs, device, opts):
+    """``Mul(gelu_erf(s0), s1)`` (operands in either order) with ``s0, s1 = Split(dense(x), 2,
+    axis = -1)`` of one bias-free dense read by nothing else -> ``_FusedMatMul(x; Wi)`` ->
+    ``_GeGLU``.  The GELU is ``match_gelu_subgraph``'s erf form; the tanh form, a
+    biased dense, another axis or an interior node read elsewhere leaves the graph alone."""
+    import types
+    from .fused import FusedMatMul, _Ctx
+    c = _Ctx(g, order, fed, fetch_refs, device, opts)
+    for name in list(order):
+        out = g.nodes.get(name)
+        if out is None or out.op != "Mul" or len(out.inputs) != 2:
+            continue
+        for k in (0, 1):
+            sp = g.nodes.get(out.inputs[k][0])
+            if sp is not None and sp.op == "Split" and out.inputs[k] == (sp.name, 1) and len(sp.inputs) == 2 and \
+                    int(sp.attr("num_split", 0)) == 2 and _ints(g, sp.inputs[0]) in ([-1], [1]):
+                break
+        else:
+            continue
+        ds = _dense_src(g, c, sp.inputs[1])
+        if ds is None or len(ds[3]) != 1 or ds[1].shape[1] % 2:
+            continue                  # (one MatMul node: no bias)
+        # the GELU over output 0: the matcher wants every reader of the Split inside it, and ``out`` reads output 1
+        readers = c.cons.get(sp.name, [])
+        if [e for e in readers if e[2] == 1] != [(out.name, k, 1)]:
+            continue
+        view = types.SimpleNamespace(g=g, fetch_nodes=c.fetch_nodes,
+                                     cons={**c.cons, sp.name: [e for e in readers if e[2] == 0]})
+        m = match_gelu_subgraph(g, view, sp.name)
+        if m is None or m[0] != "gelu_erf" or (m[2].name, 0) != out.inputs[1 - k]:
+            continue
+        interior = m[1] + [m[2], sp] + ds[3]
+        if not _interior_ok(c, interior, out):
+            continue
+        mm_name = g.unique_name(out.name + "/gate_up")
+        g.add(Node(name=mm_name, op="_FusedMatMul", inputs=[ds[0]],
+                   attrs={"_impl": FusedMatMul(ds[1], None, "none", False, device, c.use_hip, mm_name)}))
+        _remove(g, interior)
+        out.op = "_GeGLU"
+        out.inputs = [(mm_name, 0)]
+        out.ctrl = []
+        out.attrs = {"_impl": GeGLUOp(int(ds[1].shape[1]) // 2, c.use_hip)}
+        c.refresh()
+
+
+def modernbert_passes():
+    """TFSERVE_MODERNBERT=0 (read at every compile) removes the two passes: the engine A/B in one build."""
+    return [] if os.environ.get("TFSERVE_MODERNBERT", "1") == "0" else [fuse_rope_encoder_attention, fuse_geglu]
+
+
 def _reshape_to(g, n: Optional[Node], want: Sequence[int]) -> bool:
     return n is not None and n.op == "Reshape" and _ints(g, n.inputs[1]) == list(want)
 
@@ -2012,7 +2278,7 @@ def dlrm_passes():
 
 def bert_passes():
     return [fuse_layernorm, fuse_rmsnorm, fuse_embedding, fuse_window_attention, fold_window_layout, fuse_rope_attention,
-            fuse_causal_attention, fuse_attention, fuse_key_mask, fuse_swiglu]
+            fuse_causal_attention, fuse_attention, fuse_key_mask, fuse_swiglu] + modernbert_passes()
 
 
 def late_passes():

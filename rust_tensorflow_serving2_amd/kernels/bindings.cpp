@@ -1207,6 +1207,50 @@ Tensor rope_gqa_attention(const Tensor& qkv, const Tensor& cos, const Tensor& si
   return y;
 }
 
+Tensor rope_attention(const Tensor& qkv, const Tensor& cos, const Tensor& sin, const c10::optional<Tensor>& key_adder,
+                      int64_t heads, double scale, int64_t window, const c10::optional<Tensor>& out) {
+  need(qkv, at::kBFloat16, "qkv");
+  need(cos, at::kFloat, "cos");
+  need(sin, at::kFloat, "sin");
+  TORCH_CHECK(qkv.dim() == 3, "rope_attention: qkv must be [B, S, 3*H*D]");
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(qkv.device());
+  const int64_t B = qkv.size(0), S = qkv.size(1), W = qkv.size(2);
+  TORCH_CHECK(heads >= 1 && W % (3 * heads) == 0, "rope_attention: qkv width must be 3*heads*head_dim");
+  const int64_t D = W / (3 * heads);
+  TORCH_CHECK(D == 64, "rope_attention kernel supports head_dim 64, got ", D);
+  TORCH_CHECK(tfsk::rope_attention_supported(S, D, heads, window), "rope_attention kernel supports 1 <= S <= ",
+              tfsk::kMaxAttentionSeq, ", got S = ", S);
+  TORCH_CHECK(S * W * 2 < (int64_t(1) << 31) && B * heads < (int64_t(1) << 31),
+              "rope_attention: one image's qkv rows exceed 2 GiB");
+  TORCH_CHECK(aligned16(qkv), "rope_attention: qkv must be 16-byte aligned");
+  TORCH_CHECK(cos.dim() == 2 && cos.size(0) == S && cos.size(1) == D / 2 && sin.dim() == 2 && sin.size(0) == S &&
+                  sin.size(1) == D / 2,
+              "rope_attention: cos / sin must be [S, ", D / 2, "]");
+  TORCH_CHECK(cos.device() == qkv.device() && sin.device() == qkv.device(),
+              "rope_attention: cos / sin are on another device");
+  TORCH_CHECK(aligned16(cos) && aligned16(sin), "rope_attention: cos / sin must be 16-byte aligned");
+  const float* ap = nullptr;
+  int64_t bstride = 0;
+  if (key_adder.has_value()) {
+    need(*key_adder, at::kFloat, "key_adder");
+    TORCH_CHECK(key_adder->dim() == 2 && key_adder->size(1) == S && (key_adder->size(0) == B || key_adder->size(0) == 1),
+                "rope_attention: key_adder must be [B, S] or [1, S]");
+    TORCH_CHECK(key_adder->device() == qkv.device(), "rope_attention: key_adder is on another device");
+    bstride = key_adder->size(0) == 1 ? 0 : S;
+    ap = key_adder->data_ptr<float>();
+  }
+  Tensor y = out.has_value() ? *out : torch::empty({B, S, heads * D}, qkv.options());
+  need(y, at::kBFloat16, "out");
+  TORCH_CHECK(y.device() == qkv.device() && y.numel() == B * S * heads * D, "rope_attention: out has the wrong size");
+  TORCH_CHECK(aligned16(y), "rope_attention: out must be 16-byte aligned");
+  // any int is a window: one past the last key says the same as a larger one
+  const int w = window < 0 ? -1 : int(std::min<int64_t>(window, S));
+  check(tfsk::rope_attention_launch(bf16p(qkv), cos.data_ptr<float>(), sin.data_ptr<float>(), ap, bf16p_mut(y), int(B),
+                                    int(S), int(heads), int(D), w, float(scale), bstride, cur_stream(qkv)),
+        "rope_attention");
+  return y;
+}
+
 Tensor rmsnorm(const Tensor& x, const Tensor& gamma, double eps, const c10::optional<Tensor>& residual,
                const c10::optional<Tensor>& out, const c10::optional<Tensor>& sum_out) {
   need(x, at::kBFloat16, "x");
@@ -1252,6 +1296,19 @@ Tensor swiglu(const Tensor& gu, const c10::optional<Tensor>& out) {
   TORCH_CHECK(y.numel() == M * F && y.device() == gu.device(), "swiglu: out has the wrong size");
   TORCH_CHECK(aligned16(gu) && aligned16(y), "swiglu: tensors must be 16-byte aligned");
   check(tfsk::swiglu_launch(bf16p(gu), bf16p_mut(y), M, int(F), cur_stream(gu)), "swiglu");
+  return y;
+}
+
+Tensor geglu(const Tensor& gu, const c10::optional<Tensor>& out) {
+  need(gu, at::kBFloat16, "gu");
+  TORCH_CHECK(gu.dim() == 2 && gu.size(1) >= 16 && gu.size(1) % 16 == 0, "geglu: gu must be [M, 2F] with F % 8 == 0");
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(gu.device());
+  const int64_t M = gu.size(0), F = gu.size(1) / 2;
+  Tensor y = out.has_value() ? *out : torch::empty({M, F}, gu.options());
+  need(y, at::kBFloat16, "out");
+  TORCH_CHECK(y.numel() == M * F && y.device() == gu.device(), "geglu: out has the wrong size");
+  TORCH_CHECK(aligned16(gu) && aligned16(y), "geglu: tensors must be 16-byte aligned");
+  check(tfsk::geglu_launch(bf16p(gu), bf16p_mut(y), M, int(F), cur_stream(gu)), "geglu");
   return y;
 }
 
@@ -1597,6 +1654,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           return tfsk::rope_gqa_attention_supported(S, D, heads, kv_heads);
         }, py::arg("S"), py::arg("D"), py::arg("heads"), py::arg("kv_heads"),
         "whether rope_gqa_attention takes length S with heads of width D in groups of heads / kv_heads");
+  m.def("rope_attention", &rope_attention, py::arg("qkv"), py::arg("cos"), py::arg("sin"),
+        py::arg("key_adder") = py::none(), py::arg("heads"), py::arg("scale"), py::arg("window") = -1,
+        py::arg("out") = py::none(),
+        "bidirectional attention over packed qkv [B, S, 3*H*64] (Q | K | V heads): q and k are rotated by position "
+        "with the rotate-half tables cos / sin f32 [S, 32] while they are loaded; key j is open for query i iff "
+        "|i - j| <= window, window < 0 (or >= S - 1) opens every key; key_adder an optional f32 [B, S] | [1, S]");
+  m.def("rope_attention_supported",
+        [](int64_t S, int64_t D, int64_t heads, int64_t window) {
+          return tfsk::rope_attention_supported(S, D, heads, window);
+        }, py::arg("S"), py::arg("D"), py::arg("heads"), py::arg("window") = -1,
+        "whether rope_attention takes length S with heads of width D and this window");
+  m.def("geglu", &geglu, py::arg("gu"), py::arg("out") = py::none(),
+        "bf16(gelu_erf(gu[:, :F]) * gu[:, F:]) for gu [M, 2F] bf16, F % 8 == 0");
   m.def("rmsnorm", &rmsnorm, py::arg("x"), py::arg("gamma"), py::arg("eps"), py::arg("residual") = py::none(),
         py::arg("out") = py::none(), py::arg("sum_out") = py::none(),
         "bf16((x + residual) * rsqrt(mean((x + residual)^2) + eps) * gamma) over the last dim (C % 8 == 0), the row in "

@@ -378,6 +378,22 @@ hipError_t rope_gqa_attention128_launch(const uint16_t* qkv, const float* cos_t,
                                         const float* key_adder, uint16_t* ctx, int B, int S, int H, int Hkv,
                                         float scale, long adder_bstride, hipStream_t stream);
 
+// Bidirectional attention with rotary embedding at load and an optional local window
+// (kernels/rattn.hip): qkv [B][S][3*H*64] bf16 (Q heads | K heads | V heads), cos / sin f32 [S][32]
+// as above, q and k rotated in fp32 and rounded to bf16 once, then
+// ctx[b,i,h,:] = softmax over the open keys of (q~ k~^T * scale + key_adder) V.  Key j is open for
+// query i iff |i - j| <= window; window < 0 opens every key, and so does window >= S - 1, which
+// takes the same global kernel.  Closed keys weigh exactly 0.  key_adder as in causal_attention_launch.
+// D = 64, 1 <= S <= kMaxAttentionSeq, window any int; qkv, ctx and the tables 16-B aligned, one
+// image's qkv rows below 2 GiB.
+// Anything else is hipErrorInvalidValue and launches nothing.
+constexpr bool rope_attention_supported(int64_t S, int64_t D, int64_t H, int64_t /*window: every value is taken*/) {
+  return D == 64 && S >= 1 && S <= kMaxAttentionSeq && H >= 1;
+}
+hipError_t rope_attention_launch(const uint16_t* qkv, const float* cos_t, const float* sin_t, const float* key_adder,
+                                 uint16_t* ctx, int B, int S, int H, int D, int window, float scale,
+                                 long adder_bstride, hipStream_t stream);
+
 // RMSNorm over the last dim (kernels/llama.hip): y = bf16((x + r) * rsqrt(mean((x + r)^2) + eps) * gamma),
 // the row kept in fp32; r an optional residual (null: none), sum an optional second output bf16(x + r)
 // (null: not stored).  cols % 8 == 0, every pointer 16-B aligned; else hipErrorInvalidValue.
@@ -385,6 +401,8 @@ hipError_t rmsnorm_launch(const uint16_t* x, const uint16_t* r, const float* gam
                           int rows, int cols, float eps, hipStream_t stream);
 // SwiGLU (kernels/llama.hip): y[m][f] = bf16(swish(gu[m][f]) * gu[m][F + f]) in fp32, gu [M][2F], F % 8 == 0.
 hipError_t swiglu_launch(const uint16_t* gu, uint16_t* y, long M, int F, hipStream_t stream);
+// GeGLU (kernels/llama.hip): y[m][f] = bf16(gelu_erf(gu[m][f]) * gu[m][F + f]) in fp32; shapes and rejections as swiglu_launch.
+hipError_t geglu_launch(const uint16_t* gu, uint16_t* y, long M, int F, hipStream_t stream);
 
 // Windowed attention (Swin) over a packed QKV buffer [R][3*H*32] (bf16):
 // out[row, h, :] = softmax(Q K^T * scale + bias[h] (+ mask[w])) V within each

@@ -1,5 +1,6 @@
-// RMSNorm and SwiGLU for Llama-style decoders, gfx950.  All bf16 traffic is
-// 16-B vectorised (8 elements per lane and access).
+// RMSNorm and SwiGLU for Llama-style decoders and GeGLU for ModernBERT-style
+// encoders, gfx950.  All bf16 traffic is 16-B vectorised (8 elements per lane
+// and access).
 //
 // rmsnorm: y = bf16((x + r) * rsqrt(mean((x + r)^2) + eps) * gamma), optionally
 // also sum = bf16(x + r) (the residual stream the next block adds to).  A row
@@ -14,6 +15,10 @@
 // ONE GEMM over the concatenated [gate | up] weights; fp32, the sigmoid spelled
 // as in the swish epilogue (common.h sigmoid()).  One 16-B chunk of each half
 // per thread.
+//
+// geglu: the same launch with the gate's activation the erf GELU,
+// y[m][f] = bf16(0.5 g (1 + erf(g / sqrt 2)) * u), spelled as the GEMM epilogues
+// spell it (common.h kActGeluErf).
 
 #include "common.h"
 #include "launch.h"
@@ -125,8 +130,9 @@ __global__ __launch_bounds__(256) void rmsnorm_stream_kernel(const uint16_t* __r
   }
 }
 
-__global__ __launch_bounds__(256) void swiglu_kernel(const uint16_t* __restrict__ gu, uint16_t* __restrict__ y,
-                                                     long chunks, int F) {
+template <int ACT>
+__global__ __launch_bounds__(256) void glu_kernel(const uint16_t* __restrict__ gu, uint16_t* __restrict__ y,
+                                                  long chunks, int F) {
   const long i = long(blockIdx.x) * 256 + threadIdx.x;
   if (i >= chunks) return;
   const int per_row = F / 8;
@@ -137,7 +143,7 @@ __global__ __launch_bounds__(256) void swiglu_kernel(const uint16_t* __restrict_
   unpack8(*reinterpret_cast<const uint4*>(row + c), g);
   unpack8(*reinterpret_cast<const uint4*>(row + F + c), u);
 #pragma unroll
-  for (int e = 0; e < 8; ++e) o[e] = g[e] * sigmoid(g[e]) * u[e];
+  for (int e = 0; e < 8; ++e) o[e] = act_fn<ACT>(g[e]) * u[e];
   *reinterpret_cast<uint4*>(y + m * F + c) = pack8(o);
 }
 
@@ -170,15 +176,28 @@ hipError_t rmsnorm_launch(const uint16_t* x, const uint16_t* r, const float* gam
   return hipGetLastError();
 }
 
-hipError_t swiglu_launch(const uint16_t* gu, uint16_t* y, long M, int F, hipStream_t s) {
+namespace {
+
+template <int ACT>
+hipError_t glu_run(const uint16_t* gu, uint16_t* y, long M, int F, hipStream_t s) {
   if (M < 0 || F < 8 || F % 8 || gu == nullptr || y == nullptr) return hipErrorInvalidValue;
   if ((reinterpret_cast<uintptr_t>(gu) | reinterpret_cast<uintptr_t>(y)) & 15) return hipErrorInvalidValue;
   const long chunks = M * (F / 8);
   if (chunks == 0) return hipSuccess;
   const long grid = (chunks + 255) / 256;
   if (grid >= (1L << 31)) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(swiglu_kernel, dim3(unsigned(grid)), dim3(256), 0, s, gu, y, chunks, F);
+  hipLaunchKernelGGL(glu_kernel<ACT>, dim3(unsigned(grid)), dim3(256), 0, s, gu, y, chunks, F);
   return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t swiglu_launch(const uint16_t* gu, uint16_t* y, long M, int F, hipStream_t s) {
+  return glu_run<kActSwish>(gu, y, M, F, s);
+}
+
+hipError_t geglu_launch(const uint16_t* gu, uint16_t* y, long M, int F, hipStream_t s) {
+  return glu_run<kActGeluErf>(gu, y, M, F, s);
 }
 
 }  // namespace tfsk
