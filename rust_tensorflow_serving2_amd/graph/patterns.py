@@ -1060,13 +1060,22 @@ class RopeGQAttentionOp:
     absent or [B | 1, 1, 1, S], one ``rope_gqa_attention`` launch (kernels/gqattn.hip
     for 64-wide heads, kernels/gqattn128.hip for 128-wide ones): it rotates in fp32 and rounds to bf16 once, and closes masked keys with
     -inf (docs/numerics.md, "RoPE + GQA attention").  Anywhere else the graph's
-    own arithmetic with torch, in fp32."""
+    own arithmetic with torch, in fp32.
 
-    def __init__(self, heads, kv_heads, head_dim, seq, scale, closed, cos, sin, device, use_hip):
+    ``qk_norm`` = (q_gamma [D], k_gamma [D], eps): each head's q row and k row is
+    RMS-normalised before its rotation (Qwen3).  The launch takes it for D = 128
+    (docs/numerics.md, "QK-norm"); 64-wide heads take the torch path."""
+
+    def __init__(self, heads, kv_heads, head_dim, seq, scale, closed, cos, sin, device, use_hip, qk_norm=None):
         self.h, self.hkv, self.d, self.s = heads, kv_heads, head_dim, seq
         self.scale, self.closed, self.use_hip = scale, closed, use_hip
         self.cos = to_device(cos.float().contiguous(), device)
         self.sin = to_device(sin.float().contiguous(), device)
+        self.qk_norm = None
+        if qk_norm is not None:
+            qg, kg, eps = qk_norm
+            self.qk_norm = (to_device(qg.float().reshape(-1).contiguous(), device),
+                            to_device(kg.float().reshape(-1).contiguous(), device), float(eps))
 
     def __call__(self, ctx, node, ins):
         qkv = O.to_torch(ins[0])
@@ -1079,12 +1088,15 @@ class RopeGQAttentionOp:
         key_adder = adder is None or (adder.dim() == 4 and tuple(adder.shape[1:]) == (1, 1, S) and
                                       adder.shape[0] in (1, B))
         if self.use_hip and qkv.is_cuda and D in ROPE_HEAD_DIMS and H // K in ROPE_GROUPS and 1 <= S <= MAX_ATTENTION_SEQ and \
-                key_adder:
+                key_adder and (self.qk_norm is None or D == 128):
             from ..ops import hip
             from .fused import _to_bf16
             q3 = _to_bf16(qkv).reshape(B, S, W).contiguous()
             ka = None if adder is None else adder.float().reshape(-1, S).contiguous().to(qkv.device)
-            y = hip().rope_gqa_attention(q3, self.cos, self.sin, ka, H, K, self.scale)
+            if self.qk_norm is None:
+                y = hip().rope_gqa_attention(q3, self.cos, self.sin, ka, H, K, self.scale)
+            else:
+                y = hip().rope_gqa_attention(q3, self.cos, self.sin, ka, H, K, self.scale, None, *self.qk_norm)
             return [y.reshape(B * S, H * D)]
         f = qkv.float().reshape(B, S, W)
         cos = torch.cat([self.cos, self.cos], -1).to(f.device)
@@ -1095,7 +1107,13 @@ class RopeGQAttentionOp:
 
         def rot(t):
             return t * cos + torch.cat([-t[..., D // 2:], t[..., :D // 2]], -1) * sin
-        q, k = rot(heads(f[..., :H * D], H)), rot(heads(f[..., H * D:(H + K) * D], K))
+
+        def norm(t, gamma):
+            if self.qk_norm is None:
+                return t
+            return t * torch.rsqrt((t * t).mean(-1, keepdim=True) + self.qk_norm[2]) * gamma.to(t.device)
+        qg, kg = self.qk_norm[:2] if self.qk_norm is not None else (None, None)
+        q, k = rot(norm(heads(f[..., :H * D], H), qg)), rot(norm(heads(f[..., H * D:(H + K) * D], K), kg))
         v = heads(f[..., (H + K) * D:], K)
         sc = q @ k.transpose(-1, -2) * self.scale
         band = torch.ones(S, S, dtype=torch.bool, device=sc.device).tril()
@@ -1228,6 +1246,20 @@ def _group_heads_of(g, c, ref):
     return r5.inputs[0], S, H, D, H // G, nodes + [tile, r5]
 
 
+def _qk_norm_of(g, c, ref, S, n, D):
+    """ref = _RMSNorm(Reshape(dense, [-1, S, n, D])) as fuse_rmsnorm made it, with one input (no
+    residual), a gamma of D elements and output 1 unread -> (dense ref, gamma [D], eps, nodes), else None."""
+    norm = _node(g, ref)
+    if norm is None or norm.op != "_RMSNorm" or len(norm.inputs) != 1:
+        return None
+    impl = norm.attrs.get("_impl")
+    r = _node(g, norm.inputs[0])
+    if not isinstance(impl, RMSNormOp) or impl.g.numel() != D or r is None or r.op != "Reshape" or \
+            _ints(g, r.inputs[1]) != [-1, S, n, D] or any(i != 0 for _cn, _p, i in c.cons.get(norm.name, [])):
+        return None
+    return r.inputs[0], impl.g.detach().cpu(), impl.eps, [norm, r]
+
+
 def fuse_rope_attention(g, order, fed, fetch_refs, device, opts):
     """Llama's attention core -> _FusedQKV -> _RopeGQAttention: fuse_causal_attention's
     skeleton (``_causal_core``: the same masks, scale spellings and optional adder) with
@@ -1235,7 +1267,10 @@ def fuse_rope_attention(g, order, fed, fetch_refs, device, opts):
     * q and k each rotated by position (``_rope_of``), with the same tables, of the pattern's S;
     * k and v each repeated for its group of query heads before the head transpose
       (``_group_heads_of``; no Tile when the group is one head), q not;
-    * q, k, v from three denses on one input, H * D, Hkv * D and Hkv * D wide.
+    * q, k, v from three denses on one input, H * D, Hkv * D and Hkv * D wide;
+    * optionally (Qwen3's QK-norm) q and k each through ``_RMSNorm(Reshape(dense, [-1, S, n, D]))``
+      before the repeat (``_qk_norm_of``): both or neither, with one eps, v never; the op then
+      carries ``qk_norm``.  TFSERVE_QKNORM=0 (read at every compile) leaves such cores alone.
 
     Runs before fuse_causal_attention and takes nothing it takes: q and k must
     both be rotated.  A table whose halves differ, tables of another S or that
@@ -1263,9 +1298,14 @@ def fuse_rope_attention(g, order, fed, fetch_refs, device, opts):
                 _ints(g, out.inputs[1]) != [-1, H * D]:
             continue
         interior += rq[3] + rk[3] + hq[5] + hk[5] + hv[5]
+        q_src, k_src, qk_norm = hq[0], hk[0], None
+        nq, nk = _qk_norm_of(g, c, q_src, S, H, D), _qk_norm_of(g, c, k_src, S, K, D)
+        if nq is not None and nk is not None and nq[2] == nk[2] and os.environ.get("TFSERVE_QKNORM", "1") != "0":
+            q_src, k_src, qk_norm = nq[0], nk[0], (nq[1], nk[1], nq[2])
+            interior += nq[3] + nk[3]
         if adder_ref is not None and adder_ref[0] in {n.name for n in interior}:
             continue
-        dq, dk, dv = _dense_src(g, c, hq[0]), _dense_src(g, c, hk[0]), _dense_src(g, c, hv[0])
+        dq, dk, dv = _dense_src(g, c, q_src), _dense_src(g, c, k_src), _dense_src(g, c, hv[0])
         if not (dq and dk and dv and dq[0] == dk[0] == dv[0]) or \
                 [d[1].shape[1] for d in (dq, dk, dv)] != [H * D, K * D, K * D]:
             continue
@@ -1280,7 +1320,7 @@ def fuse_rope_attention(g, order, fed, fetch_refs, device, opts):
         out.op = "_RopeGQAttention"
         out.inputs = [(qkv_name, 0)] + ([adder_ref] if adder_ref is not None else [])
         out.ctrl = []
-        out.attrs = {"_impl": RopeGQAttentionOp(H, K, D, S, scale, closed, rq[1], rq[2], device, c.use_hip)}
+        out.attrs = {"_impl": RopeGQAttentionOp(H, K, D, S, scale, closed, rq[1], rq[2], device, c.use_hip, qk_norm)}
         c.refresh()
 
 

@@ -1161,7 +1161,8 @@ Tensor causal_attention(const Tensor& qkv, const c10::optional<Tensor>& key_adde
 
 Tensor rope_gqa_attention(const Tensor& qkv, const Tensor& cos, const Tensor& sin,
                           const c10::optional<Tensor>& key_adder, int64_t heads, int64_t kv_heads, double scale,
-                          const c10::optional<Tensor>& out) {
+                          const c10::optional<Tensor>& out, const c10::optional<Tensor>& q_norm,
+                          const c10::optional<Tensor>& k_norm, double norm_eps) {
   need(qkv, at::kBFloat16, "qkv");
   need(cos, at::kFloat, "cos");
   need(sin, at::kFloat, "sin");
@@ -1200,9 +1201,24 @@ Tensor rope_gqa_attention(const Tensor& qkv, const Tensor& cos, const Tensor& si
   need(y, at::kBFloat16, "out");
   TORCH_CHECK(y.device() == qkv.device() && y.numel() == B * S * heads * D, "rope_gqa_attention: out has the wrong size");
   TORCH_CHECK(aligned16(y), "rope_gqa_attention: out must be 16-byte aligned");
+  const float *qg = nullptr, *kg = nullptr;
+  TORCH_CHECK(q_norm.has_value() == k_norm.has_value(), "rope_gqa_attention: q_norm and k_norm go together");
+  if (q_norm.has_value()) {
+    TORCH_CHECK(D == 128, "rope_gqa_attention: qk norm needs head_dim 128, got ", D);
+    need(*q_norm, at::kFloat, "q_norm");
+    need(*k_norm, at::kFloat, "k_norm");
+    TORCH_CHECK(q_norm->dim() == 1 && q_norm->size(0) == D && k_norm->dim() == 1 && k_norm->size(0) == D,
+                "rope_gqa_attention: q_norm / k_norm must be [", D, "]");
+    TORCH_CHECK(q_norm->device() == qkv.device() && k_norm->device() == qkv.device(),
+                "rope_gqa_attention: q_norm / k_norm are on another device");
+    TORCH_CHECK(aligned16(*q_norm) && aligned16(*k_norm), "rope_gqa_attention: q_norm / k_norm must be 16-byte aligned");
+    TORCH_CHECK(norm_eps > 0.0, "rope_gqa_attention: norm_eps must be > 0 with a qk norm, got ", norm_eps);
+    qg = q_norm->data_ptr<float>();
+    kg = k_norm->data_ptr<float>();
+  }
   check(tfsk::rope_gqa_attention_launch(bf16p(qkv), cos.data_ptr<float>(), sin.data_ptr<float>(), ap, bf16p_mut(y),
                                         int(B), int(S), int(heads), int(kv_heads), int(D), float(scale), bstride,
-                                        cur_stream(qkv)),
+                                        cur_stream(qkv), qg, kg, float(norm_eps)),
         "rope_gqa_attention");
   return y;
 }
@@ -1645,15 +1661,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "whether causal_attention takes length S with heads of width D");
   m.def("rope_gqa_attention", &rope_gqa_attention, py::arg("qkv"), py::arg("cos"), py::arg("sin"),
         py::arg("key_adder") = py::none(), py::arg("heads"), py::arg("kv_heads"), py::arg("scale"),
-        py::arg("out") = py::none(),
+        py::arg("out") = py::none(), py::arg("q_norm") = py::none(), py::arg("k_norm") = py::none(),
+        py::arg("norm_eps") = 0.0,
         "causal grouped-query attention over packed qkv [B, S, (H + 2*Hkv)*64] (Q | K | V heads): q and k are rotated "
         "by position with the rotate-half tables cos / sin f32 [S, 32] while they are loaded, query head h reads K / V "
-        "head h / (H / Hkv), H / Hkv in {1, 2, 4, 8}; key_adder an optional f32 [B, S] | [1, S]");
+        "head h / (H / Hkv), H / Hkv in {1, 2, 4, 8}; key_adder an optional f32 [B, S] | [1, S]; with q_norm / k_norm "
+        "(f32 [128], 128-wide heads only) each head's q and k row is RMS-normalised with norm_eps before the rotation");
   m.def("rope_gqa_attention_supported",
-        [](int64_t S, int64_t D, int64_t heads, int64_t kv_heads) {
-          return tfsk::rope_gqa_attention_supported(S, D, heads, kv_heads);
-        }, py::arg("S"), py::arg("D"), py::arg("heads"), py::arg("kv_heads"),
-        "whether rope_gqa_attention takes length S with heads of width D in groups of heads / kv_heads");
+        [](int64_t S, int64_t D, int64_t heads, int64_t kv_heads, bool qk_norm) {
+          return tfsk::rope_gqa_attention_supported(S, D, heads, kv_heads, qk_norm);
+        }, py::arg("S"), py::arg("D"), py::arg("heads"), py::arg("kv_heads"), py::arg("qk_norm") = false,
+        "whether rope_gqa_attention takes length S with heads of width D in groups of heads / kv_heads, "
+        "with a QK-norm if qk_norm");
   m.def("rope_attention", &rope_attention, py::arg("qkv"), py::arg("cos"), py::arg("sin"),
         py::arg("key_adder") = py::none(), py::arg("heads"), py::arg("scale"), py::arg("window") = -1,
         py::arg("out") = py::none(),

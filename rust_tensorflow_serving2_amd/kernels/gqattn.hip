@@ -351,9 +351,12 @@ hipError_t launch_gqa(const uint16_t* qkv, const float* cos_t, const float* sin_
 
 hipError_t rope_gqa_attention_launch(const uint16_t* qkv, const float* cos_t, const float* sin_t,
                                      const float* key_adder, uint16_t* ctx, int B, int S, int H, int Hkv, int Dh,
-                                     float scale, long adder_bstride, hipStream_t st) {
+                                     float scale, long adder_bstride, hipStream_t st, const float* q_gamma,
+                                     const float* k_gamma, float eps) {
   if (Dh == 128)                                 // 128-wide heads: gqattn128.hip
-    return rope_gqa_attention128_launch(qkv, cos_t, sin_t, key_adder, ctx, B, S, H, Hkv, scale, adder_bstride, st);
+    return rope_gqa_attention128_launch(qkv, cos_t, sin_t, key_adder, ctx, B, S, H, Hkv, scale, adder_bstride, st,
+                                        q_gamma, k_gamma, eps);
+  if (q_gamma != nullptr || k_gamma != nullptr) return hipErrorInvalidValue;   // QK-norm: D = 128 only
   if (Dh != D || !rope_gqa_attention_supported(S, Dh, H, Hkv) || B < 0 || qkv == nullptr || ctx == nullptr ||
       cos_t == nullptr || sin_t == nullptr)
     return hipErrorInvalidValue;

@@ -69,6 +69,28 @@
 //     2    256      188    32     0        70,144   2 by registers; 2 workgroups per CU
 //     4    256      188    32     0        70,144   2 by registers; 2 workgroups per CU
 //     8    512      150    0      0        70,144   3 by registers; 1 workgroup per CU
+//
+// QK-norm (NORM builds; Qwen3, OLMo-2, Gemma-3): each head's q row and k row is
+// RMS-normalised over its 128 dims, x^ = x * rsqrt(mean(x^2) + eps) * gamma with
+// q_gamma / k_gamma f32 [128], before it is rotated; x^ stays in fp32 and the
+// rotation's rounding to bf16 is the only one (rope::norm_rotate8).  It rides on
+// the staging above and reads qkv no second time.  K: a key's 128 dims are the
+// registers of the eight lanes tid ^ 0 .. 7 in land(), so the sum of squares is
+// 16 FMAs and three __shfl_xor steps (1, 2, 4): no LDS, no further barrier, once
+// per key and workgroup.  Q: a row's dims are in the four lanes fr + 16 fq; both
+// chunk pairs are loaded before either is rotated and the sum crosses fq (16,
+// 32).  A dead row's zeros stay zero: 0 * rsqrt(eps), eps > 0.  k_gamma: a
+// thread's kc is fixed, so its 16 values are read once and kept in registers.
+// The other choice, a 512-B LDS array, was not needed: the register builds
+// below have no scratch and keep two waves per SIMD, and LDS reads would sit
+// between land()'s wait and its barrier, the one place all waves wait on.
+//     G    threads  VGPRs  AGPRs  scratch  LDS      waves / SIMD          (NORM)
+//     1    256      214    32     0        70,144   2 by registers; 2 workgroups per CU
+//     2    256      214    32     0        70,144   2 by registers; 2 workgroups per CU
+//     4    256      214    32     0        70,144   2 by registers; 2 workgroups per CU
+//     8    512      206    0      0        70,144   2 by registers; 1 workgroup per CU
+// The NORM = false builds are instruction for instruction what they were before
+// the parameter existed (scripts/isa_audit.py --resources, the code digest).
 // Measured against what the op ran before (torch, fp32) and against torch RoPE
 // + scaled_dot_product_attention: docs/benchmarks.md, "Llama", D = 128.
 
@@ -82,7 +104,9 @@ namespace tfsk {
 namespace {
 
 using rope::kLog2e;
+using rope::norm_rotate8;
 using rope::rotate8;
+using rope::sumsq16;
 
 constexpr int D = 128;
 constexpr int KB = 64;                  // keys per block
@@ -105,11 +129,11 @@ struct Split {
   static_assert(NW * 16 * D * 2 <= 2 * KS_BYTES, "the output strips fit in the K buffers");
 };
 
-template <int G>
+template <int G, bool NORM>
 __global__ __launch_bounds__(Split<G>::T) void rope_gqa_attention128_kernel(
     const uint16_t* __restrict__ qkv, const float* __restrict__ cos_t, const float* __restrict__ sin_t,
     const float* __restrict__ key_adder, uint16_t* __restrict__ ctx, int S, int H, int Hkv, int BK, float scale,
-    long adder_bstride) {
+    long adder_bstride, const float* __restrict__ q_gamma, const float* __restrict__ k_gamma, float eps) {
   constexpr int T = Split<G>::T, QB = Split<G>::QB, NU = Split<G>::NU;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   uint16_t* const Ks = reinterpret_cast<uint16_t*>(smem);                                  // [2][key][128] swizzled, rotated
@@ -145,6 +169,18 @@ __global__ __launch_bounds__(Split<G>::T) void rope_gqa_attention128_kernel(
   const int kc = tid & 7, vch = tid & 15;
   u32x4 klo[NU], khi[NU], kcos[NU][2], ksin[NU][2], vreg[NU][2];
   float areg = 0.f;
+  // QK-norm: the thread's kc never changes, so its sixteen k_gamma values (dims 8 kc .. and 64 + 8 kc ..)
+  // are read once and stay in registers for the whole walk
+  float kg[NORM ? 2 : 1][8];
+  if constexpr (NORM) {
+#pragma unroll
+    for (int hf = 0; hf < 2; ++hf) {
+      const f32x4 a = *reinterpret_cast<const f32x4*>(k_gamma + hf * HALF + kc * 8);
+      const f32x4 c = *reinterpret_cast<const f32x4*>(k_gamma + hf * HALF + kc * 8 + 4);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) kg[hf][e] = a[e], kg[hf][4 + e] = c[e];
+    }
+  }
   auto issue = [&](int j) {
     const int k0 = j * KB;
 #pragma unroll
@@ -183,7 +219,17 @@ __global__ __launch_bounds__(Split<G>::T) void rope_gqa_attention128_kernel(
 #pragma unroll
     for (int i = 0; i < NU; ++i) {
       const int key = (tid + i * T) >> 3;
-      rotate8(klo[i], khi[i], kcos[i], ksin[i]);
+      if constexpr (NORM) {
+        // the key's 128 dims lie in the eight lanes tid ^ 0 .. 7: its sum of squares without LDS.
+        // A dead key's zeros give 0 * rsqrt(eps) = 0.
+        float ss = sumsq16(klo[i], khi[i]);
+        ss += __shfl_xor(ss, 1, 64);
+        ss += __shfl_xor(ss, 2, 64);
+        ss += __shfl_xor(ss, 4, 64);
+        norm_rotate8(klo[i], khi[i], kcos[i], ksin[i], __builtin_amdgcn_rsqf(ss * (1.f / D) + eps), kg[0], kg[1]);
+      } else {
+        rotate8(klo[i], khi[i], kcos[i], ksin[i]);
+      }
       uint16_t* kr = kbuf + key * D;
       *reinterpret_cast<u32x4*>(kr + ((kc ^ kswz(key)) * 8)) = klo[i];
       *reinterpret_cast<u32x4*>(kr + (((kc + 8) ^ kswz(key)) * 8)) = khi[i];
@@ -211,7 +257,43 @@ __global__ __launch_bounds__(Split<G>::T) void rope_gqa_attention128_kernel(
   const int q0 = qb * QB + (wid / G) * 16;
   const int hq = hk * G + wid % G;
   bf16x8 qf[4];
-  {
+  if constexpr (NORM) {
+    // a row's 128 dims lie in the four lanes fr + 16 fq: both chunk pairs are loaded before either is
+    // rotated, and the sum of squares crosses fq in two steps
+    const int row = q0 + fr;
+    const bool live = row < S;
+    u32x4 lo[2], hi[2], qcos[2][2], qsin[2][2];
+    float qg[2][2][8];
+#pragma unroll
+    for (int kk = 0; kk < 2; ++kk) {
+      const int ch = 4 * kk + fq;
+      const uint32_t to = uint32_t(row * HALF + ch * 8) * 4u;
+      const uint32_t qo = uint32_t(long(row) * row_stride + hq * D + ch * 8) * 2u;
+      qcos[kk][0] = __builtin_amdgcn_raw_buffer_load_b128(rsC, live ? to : gemm::kOOB, 0, 0);
+      qcos[kk][1] = __builtin_amdgcn_raw_buffer_load_b128(rsC, live ? to + 16u : gemm::kOOB, 0, 0);
+      qsin[kk][0] = __builtin_amdgcn_raw_buffer_load_b128(rsS, live ? to : gemm::kOOB, 0, 0);
+      qsin[kk][1] = __builtin_amdgcn_raw_buffer_load_b128(rsS, live ? to + 16u : gemm::kOOB, 0, 0);
+      lo[kk] = __builtin_amdgcn_raw_buffer_load_b128(rsQ, live ? qo : gemm::kOOB, 0, 0);
+      hi[kk] = __builtin_amdgcn_raw_buffer_load_b128(rsQ, live ? qo + HALF * 2u : gemm::kOOB, 0, 0);
+#pragma unroll
+      for (int hf = 0; hf < 2; ++hf) {
+        const f32x4 a = *reinterpret_cast<const f32x4*>(q_gamma + hf * HALF + ch * 8);
+        const f32x4 c = *reinterpret_cast<const f32x4*>(q_gamma + hf * HALF + ch * 8 + 4);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) qg[kk][hf][e] = a[e], qg[kk][hf][4 + e] = c[e];
+      }
+    }
+    float ss = sumsq16(lo[0], hi[0]) + sumsq16(lo[1], hi[1]);
+    ss += __shfl_xor(ss, 16, 64);
+    ss += __shfl_xor(ss, 32, 64);
+    const float r = __builtin_amdgcn_rsqf(ss * (1.f / D) + eps);
+#pragma unroll
+    for (int kk = 0; kk < 2; ++kk) {
+      norm_rotate8(lo[kk], hi[kk], qcos[kk], qsin[kk], r, qg[kk][0], qg[kk][1]);
+      qf[kk] = __builtin_bit_cast(bf16x8, lo[kk]);
+      qf[kk + 2] = __builtin_bit_cast(bf16x8, hi[kk]);
+    }
+  } else {
     const int row = q0 + fr;
     const bool live = row < S;
 #pragma unroll
@@ -348,16 +430,17 @@ __global__ __launch_bounds__(Split<G>::T) void rope_gqa_attention128_kernel(
   }
 }
 
-template <int G>
+template <int G, bool NORM>
 hipError_t launch_gqa128(const uint16_t* qkv, const float* cos_t, const float* sin_t, const float* adder,
                          uint16_t* ctx, long BK, int S, int H, int Hkv, float scale, long adder_bstride,
-                         hipStream_t st) {
+                         const float* q_gamma, const float* k_gamma, float eps, hipStream_t st) {
   const long grid = BK * ((S + Split<G>::QB - 1) / Split<G>::QB);
   if (grid >= (1L << 31)) return hipErrorInvalidValue;
-  hipError_t e = ensure_dyn_lds(reinterpret_cast<const void*>(&rope_gqa_attention128_kernel<G>), LDS_BYTES);
+  constexpr auto kernel = &rope_gqa_attention128_kernel<G, NORM>;
+  hipError_t e = ensure_dyn_lds(reinterpret_cast<const void*>(kernel), LDS_BYTES);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(rope_gqa_attention128_kernel<G>, dim3(unsigned(grid)), dim3(Split<G>::T), LDS_BYTES, st, qkv,
-                     cos_t, sin_t, adder, ctx, S, H, Hkv, int(BK), scale, adder_bstride);
+  hipLaunchKernelGGL(kernel, dim3(unsigned(grid)), dim3(Split<G>::T), LDS_BYTES, st, qkv, cos_t, sin_t, adder, ctx, S,
+                     H, Hkv, int(BK), scale, adder_bstride, q_gamma, k_gamma, eps);
   return hipGetLastError();
 }
 
@@ -365,7 +448,8 @@ hipError_t launch_gqa128(const uint16_t* qkv, const float* cos_t, const float* s
 
 hipError_t rope_gqa_attention128_launch(const uint16_t* qkv, const float* cos_t, const float* sin_t,
                                         const float* key_adder, uint16_t* ctx, int B, int S, int H, int Hkv,
-                                        float scale, long adder_bstride, hipStream_t st) {
+                                        float scale, long adder_bstride, hipStream_t st, const float* q_gamma,
+                                        const float* k_gamma, float eps) {
   if (!rope_gqa_attention_supported(S, D, H, Hkv) || B < 0 || qkv == nullptr || ctx == nullptr || cos_t == nullptr ||
       sin_t == nullptr)
     return hipErrorInvalidValue;
@@ -376,13 +460,24 @@ hipError_t rope_gqa_attention128_launch(const uint16_t* qkv, const float* cos_t,
   if ((reinterpret_cast<uintptr_t>(qkv) | reinterpret_cast<uintptr_t>(ctx) | reinterpret_cast<uintptr_t>(cos_t) |
        reinterpret_cast<uintptr_t>(sin_t)) & 15)
     return hipErrorInvalidValue;
+  // QK-norm: both gammas or neither, 16-B aligned (the kernel reads them as float4), eps > 0
+  const bool norm = q_gamma != nullptr || k_gamma != nullptr;
+  if (norm && (q_gamma == nullptr || k_gamma == nullptr || !(eps > 0.f) ||
+               ((reinterpret_cast<uintptr_t>(q_gamma) | reinterpret_cast<uintptr_t>(k_gamma)) & 15)))
+    return hipErrorInvalidValue;
   if (BK == 0) return hipSuccess;
+#define TFSK_GQA128(G_)                                                                                        \
+  return norm ? launch_gqa128<G_, true>(qkv, cos_t, sin_t, key_adder, ctx, BK, S, H, Hkv, scale, adder_bstride, \
+                                        q_gamma, k_gamma, eps, st)                                             \
+              : launch_gqa128<G_, false>(qkv, cos_t, sin_t, key_adder, ctx, BK, S, H, Hkv, scale, adder_bstride, \
+                                         nullptr, nullptr, 0.f, st)
   switch (H / Hkv) {
-    case 1: return launch_gqa128<1>(qkv, cos_t, sin_t, key_adder, ctx, BK, S, H, Hkv, scale, adder_bstride, st);
-    case 2: return launch_gqa128<2>(qkv, cos_t, sin_t, key_adder, ctx, BK, S, H, Hkv, scale, adder_bstride, st);
-    case 4: return launch_gqa128<4>(qkv, cos_t, sin_t, key_adder, ctx, BK, S, H, Hkv, scale, adder_bstride, st);
-    default: return launch_gqa128<8>(qkv, cos_t, sin_t, key_adder, ctx, BK, S, H, Hkv, scale, adder_bstride, st);
+    case 1: TFSK_GQA128(1);
+    case 2: TFSK_GQA128(2);
+    case 4: TFSK_GQA128(4);
+    default: TFSK_GQA128(8);
   }
+#undef TFSK_GQA128
 }
 
 }  // namespace tfsk

@@ -366,17 +366,25 @@ hipError_t causal_attention_launch(const uint16_t* qkv, const float* key_adder, 
 // causal_attention_launch.  D in {64, 128}, 1 <= S <= kMaxAttentionSeq, H % Hkv == 0 with
 // H / Hkv in {1, 2, 4, 8}; qkv, ctx and the tables 16-B aligned, one image's qkv
 // rows below 2 GiB.  Anything else is hipErrorInvalidValue and launches nothing.
-constexpr bool rope_gqa_attention_supported(int64_t S, int64_t D, int64_t H, int64_t Hkv) {
-  return (D == 64 || D == 128) && S >= 1 && S <= kMaxAttentionSeq && Hkv >= 1 && H >= Hkv && H % Hkv == 0 &&
-         (H / Hkv == 1 || H / Hkv == 2 || H / Hkv == 4 || H / Hkv == 8);
+//
+// QK-norm (Qwen3-style blocks), D = 128 only: with q_gamma and k_gamma (f32 [128], 16-B aligned,
+// both or neither) and eps > 0, each head's q row and k row is first normalised in fp32,
+// x^ = x * rsqrt(mean_d(x^2) + eps) * gamma, and x^ is what is rotated; still one rounding to bf16.
+// One gamma alone, a norm with D != 128, a misaligned gamma or eps <= 0 is hipErrorInvalidValue.
+constexpr bool rope_gqa_attention_supported(int64_t S, int64_t D, int64_t H, int64_t Hkv, bool qk_norm = false) {
+  return (D == 128 || (D == 64 && !qk_norm)) && S >= 1 && S <= kMaxAttentionSeq && Hkv >= 1 && H >= Hkv &&
+         H % Hkv == 0 && (H / Hkv == 1 || H / Hkv == 2 || H / Hkv == 4 || H / Hkv == 8);
 }
 hipError_t rope_gqa_attention_launch(const uint16_t* qkv, const float* cos_t, const float* sin_t,
                                      const float* key_adder, uint16_t* ctx, int B, int S, int H, int Hkv, int D,
-                                     float scale, long adder_bstride, hipStream_t stream);
+                                     float scale, long adder_bstride, hipStream_t stream,
+                                     const float* q_gamma = nullptr, const float* k_gamma = nullptr, float eps = 0.f);
 // the D = 128 kernels; rope_gqa_attention_launch dispatches here
 hipError_t rope_gqa_attention128_launch(const uint16_t* qkv, const float* cos_t, const float* sin_t,
                                         const float* key_adder, uint16_t* ctx, int B, int S, int H, int Hkv,
-                                        float scale, long adder_bstride, hipStream_t stream);
+                                        float scale, long adder_bstride, hipStream_t stream,
+                                        const float* q_gamma = nullptr, const float* k_gamma = nullptr,
+                                        float eps = 0.f);
 
 // Bidirectional attention with rotary embedding at load and an optional local window
 // (kernels/rattn.hip): qkv [B][S][3*H*64] bf16 (Q heads | K heads | V heads), cos / sin f32 [S][32]

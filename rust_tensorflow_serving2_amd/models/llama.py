@@ -81,9 +81,9 @@ def linear(g, x, din, dout, rng, name, std, const_weights=False):
         return g.node("MatMul", "MatMul", [x, w], T=F32, transpose_a=False, transpose_b=False)
 
 
-def rms_norm(g, x, dim, rng, eps, name):
+def rms_norm(g, x, dim, rng, eps, name, weight_std=0.05):
     with g.scope(name):
-        gamma = g.variable("weight", (1.0 + 0.05 * rng.standard_normal(dim)).astype(np.float32))
+        gamma = g.variable("weight", (1.0 + weight_std * rng.standard_normal(dim)).astype(np.float32))
         sq = g.node("Square", "Square", [x], T=F32)
         ms = g.node("Mean", "Mean", [sq, g.const("Mean/reduction_indices", np.array([-1], np.int32))], T=F32,
                     Tidx=I32, keep_dims=True)

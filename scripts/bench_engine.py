@@ -20,7 +20,7 @@ def main():
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--baseline", action="store_true")
     ap.add_argument("--model", default="resnet50", choices=["resnet50", "resnet50-v2", "resnext50", "mobilenet-v1", "mobilenet-v2", "mobilenet-v3-large",
-                                                      "mobilenet-v3-small", "efficientnet-b0", "convnext-tiny", "vit-b16", "swin-tiny", "bert-base", "modernbert-base"])
+                                                      "mobilenet-v3-small", "efficientnet-b0", "convnext-tiny", "vit-b16", "swin-tiny", "bert-base", "modernbert-base", "qwen3-0.6b"])
     ap.add_argument("--graph-tune", type=int, default=1, help="whole-graph tile re-tuning at capture (0 = off)")
     ap.add_argument("--windows", type=int, default=1,
                     help="timed windows of --iters replays each; above 1, graph_ms is their median and "
@@ -49,6 +49,15 @@ def main():
         r = s.runner("serving_default", ["input_ids", "input_mask"], ["hidden", "cls"])
         # 22 layers of GEMMs (Wqkv, Wo, Wi, MLP Wo) over S = 1024 rows + attention (8 global layers whole, 14 at 129 keys)
         flop_per_item = 2 * 22 * 768 * (4 * 768 + 3 * 1152) * 1024 + 4 * 768 * 1024 * (8 * 1024 + 14 * 129)
+    elif args.model == "qwen3-0.6b":
+        from rust_tensorflow_serving2_amd.models import qwen3
+        if not args.model_dir:
+            qwen3.export(path, "qwen3_0_6b", seed=0)
+        s = Servable("qwen3", 1, path, opts)
+        r = s.runner("serving_default", ["input_ids", "input_mask"], ["logits", "hidden"])
+        # 28 layers of GEMMs (q 2048, k and v 1024 each, o 2048 x 1024, gate / up / down 3072) over S = 1024 rows
+        # + causal attention over 16 heads of 128 (half the S x S square)
+        flop_per_item = 2 * 28 * 1024 * (2 * 2048 + 2 * 1024 + 3 * 3072) * 1024 + 2 * 28 * 2048 * 1024 * 1024
     elif args.model.startswith("mobilenet"):
         from rust_tensorflow_serving2_amd.models import mobilenet
         if not args.model_dir:
@@ -106,6 +115,8 @@ def main():
                  np.zeros((b, 128), np.int32)]
         elif args.model == "modernbert-base":
             x = [rng.integers(0, 50368, (b, 1024)).astype(np.int32), np.ones((b, 1024), np.int32)]
+        elif args.model == "qwen3-0.6b":
+            x = [rng.integers(0, 32000, (b, 1024)).astype(np.int32), np.ones((b, 1024), np.int32)]
         else:
             x = [rng.random((b, 224, 224, 3), dtype=np.float32)]
         t0 = time.perf_counter()

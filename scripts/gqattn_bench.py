@@ -19,9 +19,11 @@ graph op ran before the kernel existed, RopeGQAttentionOp with use_hip = False o
 the device (fp32, K / V repeated, [B, H, S, S] scores materialised), and (b)
 "torch sdpa": the rotation in fp32 rounded to bf16, then
 torch.nn.functional.scaled_dot_product_attention(is_causal=True) over K / V
-repeated for their groups.  ``--d128`` runs the D = 128 shape list.
+repeated for their groups.  ``--d128`` runs the D = 128 shape list.  ``--qk-norm``
+(D = 128 shapes) gives the kernel a QK-norm and times it against the op's torch
+path, the norm-less kernel and two rmsnorm launches plus the norm-less kernel.
 
-    python scripts/gqattn_bench.py [--shapes B,S,H,Hkv[,D] ...] [--d128] [--reps 21] [--rounds 5] [--json]
+    python scripts/gqattn_bench.py [--shapes B,S,H,Hkv[,D] ...] [--d128] [--qk-norm] [--reps 21] [--rounds 5] [--json]
 """
 import argparse
 import json
@@ -77,9 +79,29 @@ def sdpa(qkv, cos, sin, h, k, d, scale, out):
     out.copy_(y.transpose(1, 2).reshape(b, s, h * d))
 
 
-def candidates(H, qkv, cos, sin, h, k, d, out):
+def candidates(H, qkv, cos, sin, h, k, d, out, qk_norm=None):
     """name -> callable writing out[name]; the first is the kernel, the second what it is checked against."""
     scale = d ** -0.5
+    if qk_norm is not None:
+        from rust_tensorflow_serving2_amd.graph.patterns import RopeGQAttentionOp
+        b, s, _ = qkv.shape
+        qg, kg, eps = qk_norm
+        op = RopeGQAttentionOp(h, k, d, s, scale, -10000.0, cos, sin, qkv.device, False, qk_norm)
+        flat = qkv.reshape(b * s, -1)
+        # what the graph can launch without the fused norm: rmsnorm over q's and k's [B S n, 128] rows, then the
+        # norm-less kernel (its packed input taken as given: the copies that would pack it are not charged)
+        q_rows = qkv[..., :h * d].reshape(-1, d).contiguous()
+        k_rows = qkv[..., h * d:(h + k) * d].reshape(-1, d).contiguous()
+        qn, kn = torch.empty_like(q_rows), torch.empty_like(k_rows)
+
+        def unfused():
+            H.rmsnorm(q_rows, qg, eps, None, qn)
+            H.rmsnorm(k_rows, kg, eps, None, kn)
+            H.rope_gqa_attention(qkv, cos, sin, None, h, k, scale, out["rmsnorm x2 + no norm"])
+        return {"rope_gqa": lambda: H.rope_gqa_attention(qkv, cos, sin, None, h, k, scale, out["rope_gqa"], qg, kg, eps),
+                "op torch path": lambda: out["op torch path"].copy_(op(None, None, [flat])[0].reshape(b, s, h * d)),
+                "no norm": lambda: H.rope_gqa_attention(qkv, cos, sin, None, h, k, scale, out["no norm"]),
+                "rmsnorm x2 + no norm": unfused}
     runs = {"rope_gqa": lambda: H.rope_gqa_attention(qkv, cos, sin, None, h, k, scale, out["rope_gqa"])}
     if d == 64:
         packed = compose(qkv, cos, sin, h, k)
@@ -100,6 +122,9 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shapes", nargs="+", type=parse, default=None, metavar="B,S,H,Hkv[,D]")
     ap.add_argument("--d128", action="store_true", help="the D = 128 shape list instead of the D = 64 one")
+    ap.add_argument("--qk-norm", action="store_true",
+                    help="D = 128 with the QK-norm in the kernel, against the op's torch path, the norm-less kernel "
+                         "(the cost of the norm) and two rmsnorm launches followed by the norm-less kernel")
     ap.add_argument("--reps", type=int, default=21)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--json", action="store_true")
@@ -118,8 +143,14 @@ def main():
         qkv = torch.randn(b, s, (h + 2 * k) * d, generator=g).to(torch.bfloat16).to(dev)
         cos, sin = (torch.from_numpy(t[0, 0, :, :d // 2].copy()).to(dev) for t in llama.rope_tables(s, dim=d))
         names = ["rope_gqa", "composition", "cattn only"] if d == 64 else ["rope_gqa", "op torch path", "torch sdpa"]
+        qk_norm = None
+        if args.qk_norm:
+            if d != 128:
+                raise SystemExit("--qk-norm needs D = 128 shapes")
+            names = ["rope_gqa", "op torch path", "no norm", "rmsnorm x2 + no norm"]
+            qk_norm = tuple((1 + 0.25 * torch.randn(d, generator=g)).to(dev) for _ in range(2)) + (1e-6,)
         out = {n: torch.empty(b, s, h * d, dtype=torch.bfloat16, device=dev) for n in names}
-        runs = candidates(H, qkv, cos, sin, h, k, d, out)
+        runs = candidates(H, qkv, cos, sin, h, k, d, out, qk_norm)
         rounds = {n: [] for n in runs}
         for _ in range(args.rounds):
             for n, fn in runs.items():                       # alternating: every round times every candidate once

@@ -5,7 +5,7 @@ The reference downloads ``resnet_v2_fp32_savedmodel_NHWC`` and copies version
 Offline, we write random-init SavedModels of the same architectures in the
 same ``<root>/<name>/<version>/`` layout:
 
-    python serving/make_models.py --root serving/models [--models resnet,resnet_v2,resnext50,mobilenet,mobilenet_v2,mobilenet_v3_large,mobilenet_v3_small,efficientnet_b0,convnext_tiny,vit_b16,swin_tiny,bert,gpt2,gpt2_tiny,llama,llama_tiny,llama_8b,llama_tiny_d128,modernbert,dlrm,half_plus_two]
+    python serving/make_models.py --root serving/models [--models resnet,resnet_v2,resnext50,mobilenet,mobilenet_v2,mobilenet_v3_large,mobilenet_v3_small,efficientnet_b0,convnext_tiny,vit_b16,swin_tiny,bert,gpt2,gpt2_tiny,llama,llama_tiny,llama_8b,llama_tiny_d128,qwen3,qwen3_tiny,modernbert,dlrm,half_plus_two]
 
 * ``resnet``        ResNet-50 v1.5 (NHWC, alias "input", outputs classes/probabilities)
 * ``resnet_v2``     ResNet-50 v2 pre-activation (the fetch.sh model's architecture)
@@ -25,6 +25,9 @@ same ``<root>/<name>/<version>/`` layout:
                     last position; input_ids / input_mask) and a 2-layer, 256-wide one (4 / 2 heads) at S = 160
 * ``llama_8b`` / ``llama_tiny_d128``  the same decoder with 128-wide heads: 4096 wide, 32 layers, 32 / 8 heads, SwiGLU 14336,
                     S = 1024, vocabulary 32000 (~13 GB of fp32 weights), and a 2-layer, 512-wide one (4 / 2 heads) at S = 160
+* ``qwen3`` (= ``qwen3_0_6b``) / ``qwen3_tiny``  Qwen3-style decoder: Llama's graph with 128-wide heads whose total width is not the
+                    hidden width and a per-head RMSNorm on q and k before the rotation; 1024 wide, 28 layers, 16 / 8 heads,
+                    SwiGLU 3072, S = 1024, vocabulary 32000, and a 2-layer, 256-wide one (4 / 2 heads) at S = 160
 * ``modernbert`` (= ``modernbert_base`` and ``modernbert_tiny``)  ModernBERT-style encoder, 768 wide, 22 layers, 12 heads, GeGLU 1152,
                     S = 1024, vocabulary 50368 (pre-norm, bias-free, rotate-half RoPE in every layer, two layers in three
                     local with a +-64 band adder; input_ids / input_mask -> hidden, cls) and a 3-layer, 128-wide one at
@@ -90,6 +93,9 @@ def main(argv=None):
         elif m in ("llama", "llama_1b", "llama_tiny", "llama_8b", "llama_tiny_d128"):
             from rust_tensorflow_serving2_amd.models import llama
             llama.export(out, "llama_1b" if m == "llama" else m, seed=args.seed)
+        elif m in ("qwen3", "qwen3_0_6b", "qwen3_tiny"):
+            from rust_tensorflow_serving2_amd.models import qwen3
+            qwen3.export(out, "qwen3_0_6b" if m == "qwen3" else m, seed=args.seed)
         elif m in ("modernbert_base", "modernbert_tiny"):
             from rust_tensorflow_serving2_amd.models import modernbert
             modernbert.export(out, m, seed=args.seed)
