@@ -830,6 +830,34 @@ def _square(v: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
 def _causal_mask(g, n: Optional[Node]):
     """n = Sub(Mul(w, b), c) or SelectV2(b, w, fill) with b the exact lower-triangular band
     -> (w ref, S, the value of a masked score, nodes), else None."""
+    m = _masked_scores(g, n)
+    if m is None or not torch.equal(m[1].double(), torch.ones(m[1].shape, dtype=torch.float64).tril()):
+        return None
+    return m[0], int(m[1].shape[0]), m[2], m[3]
+
+
+def _window_mask(g, n: Optional[Node]):
+    """``_causal_mask`` for a sliding window: b's ones are exactly {0 <= i - j <= w} for one integer w >= 0
+    -> (w ref, S, the value of a masked score, nodes, window), window = -1 when the band is the whole
+    triangle (w >= S - 1), else None.  w is read off column 0, then the whole matrix is compared: a hole, a
+    band off the diagonal, an upper band or two widths in one band are not a window."""
+    m = _masked_scores(g, n)
+    if m is None:
+        return None
+    b = m[1].double()
+    S = int(b.shape[0])
+    w = int(b[:, 0].sum()) - 1
+    pos = torch.arange(S)
+    d = pos[:, None] - pos[None, :]
+    if w < 0 or not torch.equal(b, ((d >= 0) & (d <= w)).double()):
+        return None
+    return m[0], S, m[2], m[3], (w if w < S - 1 else -1)
+
+
+def _masked_scores(g, n: Optional[Node]):
+    """n = Sub(Mul(w, b), c) or SelectV2(b, w, fill) with b a constant 0/1 (or bool) [S, S] under leading 1s,
+    c = fill * (1 - b), fill strong enough -> (w ref, b, the value of a masked score, nodes), else None.
+    What b's ones must be is the caller's question."""
     if n is None:
         return None
     if n.op == "SelectV2" and len(n.inputs) == 3:
@@ -858,9 +886,7 @@ def _causal_mask(g, n: Optional[Node]):
         closed, w_ref, nodes = -fill, mul.inputs[1 - k], [n, mul]
     else:
         return None
-    if not torch.equal(b.double(), torch.ones(b.shape, dtype=torch.float64).tril()):
-        return None
-    return w_ref, int(b.shape[0]), closed, nodes
+    return w_ref, b, closed, nodes
 
 
 def _split_qkv(g, c, refs, H: int, D: int):
@@ -891,10 +917,12 @@ def _split_qkv(g, c, refs, H: int, D: int):
     return ds[0], ds[1], ds[2], nodes + ds[3]
 
 
-def _causal_core(g, out: Node):
+def _causal_core(g, out: Node, mask_of=None):
     """out = Reshape(Transpose(BatchMatMul(Softmax(scores), v), [0, 2, 1, 3]), .) with ``scores`` the causally
     masked, optionally scaled q k^T of fuse_causal_attention, with or without an adder
-    -> (qk node, pv node, S, scale, closed, adder ref | None, interior nodes), else None."""
+    -> (qk node, pv node, S, scale, closed, adder ref | None, interior nodes, window), else None.
+    ``mask_of`` is ``_causal_mask`` (the default: window is -1) or ``_window_mask``."""
+    mask_of = mask_of or _causal_mask
     t2 = _node(g, out.inputs[0])
     if t2 is None or t2.op != "Transpose" or _ints(g, t2.inputs[1]) != [0, 2, 1, 3]:
         return None
@@ -910,17 +938,18 @@ def _causal_core(g, out: Node):
     if cur is not None and cur.op in ("Add", "AddV2") and len(cur.inputs) == 2:
         for k in (0, 1):
             side = _node(g, cur.inputs[k])
-            if side is not None and side.op in ("Sub", "SelectV2") and _causal_mask(g, side) is not None:
+            if side is not None and side.op in ("Sub", "SelectV2") and mask_of(g, side) is not None:
                 break
         else:
             return None
         adder_ref = cur.inputs[1 - k]
         interior.append(cur)
         cur = side
-    cm = _causal_mask(g, cur)
+    cm = mask_of(g, cur)
     if cm is None:
         return None
-    w_ref, S, closed, nodes = cm
+    w_ref, S, closed, nodes = cm[:4]
+    window = cm[4] if len(cm) > 4 else -1
     interior += nodes
     scale = 1.0
     qk = _node(g, w_ref)
@@ -932,7 +961,7 @@ def _causal_core(g, out: Node):
     if qk is None or qk.op not in _BMM or qk.attr("adj_x", False) or not qk.attr("adj_y", False):
         return None
     interior.append(qk)
-    return qk, pv, S, scale, closed, adder_ref, interior
+    return qk, pv, S, scale, closed, adder_ref, interior, window
 
 
 def fuse_causal_attention(g, order, fed, fetch_refs, device, opts):
@@ -960,7 +989,7 @@ def fuse_causal_attention(g, order, fed, fetch_refs, device, opts):
         core = _causal_core(g, out)
         if core is None:
             continue
-        qk, pv, S, scale, closed, adder_ref, interior = core
+        qk, pv, S, scale, closed, adder_ref, interior, _window = core
         hq, hk, hv = _heads_of(g, c, qk.inputs[0]), _heads_of(g, c, qk.inputs[1]), _heads_of(g, c, pv.inputs[1])
         if hq is None or hk is None or hv is None or hq[1:4] != hk[1:4] or hq[1:4] != hv[1:4]:
             continue
@@ -1064,11 +1093,19 @@ class RopeGQAttentionOp:
 
     ``qk_norm`` = (q_gamma [D], k_gamma [D], eps): each head's q row and k row is
     RMS-normalised before its rotation (Qwen3).  The launch takes it for D = 128
-    (docs/numerics.md, "QK-norm"); 64-wide heads take the torch path."""
+    (docs/numerics.md, "QK-norm"); 64-wide heads take the torch path.
 
-    def __init__(self, heads, kv_heads, head_dim, seq, scale, closed, cos, sin, device, use_hip, qk_norm=None):
+    ``window`` >= 0 (Gemma's local layers): key j is open for query i iff
+    0 <= i - j <= window; -1 is plain causal.  D = 256 takes one
+    ``rope_gqa_attention256`` launch (kernels/gqattn256.hip) with or without a
+    norm and with any window (docs/numerics.md, "RoPE + GQA attention, D = 256");
+    a window at D in {64, 128} takes the torch path."""
+
+    def __init__(self, heads, kv_heads, head_dim, seq, scale, closed, cos, sin, device, use_hip, qk_norm=None,
+                 window=-1):
         self.h, self.hkv, self.d, self.s = heads, kv_heads, head_dim, seq
         self.scale, self.closed, self.use_hip = scale, closed, use_hip
+        self.window = -1 if window < 0 or window >= seq - 1 else int(window)
         self.cos = to_device(cos.float().contiguous(), device)
         self.sin = to_device(sin.float().contiguous(), device)
         self.qk_norm = None
@@ -1087,8 +1124,16 @@ class RopeGQAttentionOp:
         B = qkv.numel() // (S * W)
         key_adder = adder is None or (adder.dim() == 4 and tuple(adder.shape[1:]) == (1, 1, S) and
                                       adder.shape[0] in (1, B))
-        if self.use_hip and qkv.is_cuda and D in ROPE_HEAD_DIMS and H // K in ROPE_GROUPS and 1 <= S <= MAX_ATTENTION_SEQ and \
-                key_adder and (self.qk_norm is None or D == 128):
+        on_device = self.use_hip and qkv.is_cuda and H // K in ROPE_GROUPS and 1 <= S <= MAX_ATTENTION_SEQ and key_adder
+        if on_device and D == 256:
+            from ..ops import hip
+            from .fused import _to_bf16
+            q3 = _to_bf16(qkv).reshape(B, S, W).contiguous()
+            ka = None if adder is None else adder.float().reshape(-1, S).contiguous().to(qkv.device)
+            norm = self.qk_norm if self.qk_norm is not None else (None, None, 0.0)
+            y = hip().rope_gqa_attention256(q3, self.cos, self.sin, ka, H, K, self.scale, self.window, None, *norm)
+            return [y.reshape(B * S, H * D)]
+        if on_device and D in ROPE_HEAD_DIMS and self.window < 0 and (self.qk_norm is None or D == 128):
             from ..ops import hip
             from .fused import _to_bf16
             q3 = _to_bf16(qkv).reshape(B, S, W).contiguous()
@@ -1117,6 +1162,8 @@ class RopeGQAttentionOp:
         v = heads(f[..., (H + K) * D:], K)
         sc = q @ k.transpose(-1, -2) * self.scale
         band = torch.ones(S, S, dtype=torch.bool, device=sc.device).tril()
+        if self.window >= 0:
+            band = band & ~torch.ones(S, S, dtype=torch.bool, device=sc.device).tril(-self.window - 1)
         sc = torch.where(band, sc, torch.full_like(sc, self.closed))
         if adder is not None:
             sc = sc + adder.float().to(sc.device)
@@ -1271,6 +1318,9 @@ def fuse_rope_attention(g, order, fed, fetch_refs, device, opts):
     * optionally (Qwen3's QK-norm) q and k each through ``_RMSNorm(Reshape(dense, [-1, S, n, D]))``
       before the repeat (``_qk_norm_of``): both or neither, with one eps, v never; the op then
       carries ``qk_norm``.  TFSERVE_QKNORM=0 (read at every compile) leaves such cores alone.
+    * the mask either the triangle or (Gemma's local layers) a sliding window, the band {0 <= i - j <= w}
+      for one w >= 0 in the same two spellings (``_window_mask``); the op then carries ``window`` = w.
+      TFSERVE_GEMMA=0 (read at every compile) leaves windowed cores alone.
 
     Runs before fuse_causal_attention and takes nothing it takes: q and k must
     both be rotated.  A table whose halves differ, tables of another S or that
@@ -1279,14 +1329,15 @@ def fuse_rope_attention(g, order, fed, fetch_refs, device, opts):
     match it either: ``_heads_of`` finds an AddV2 or a Tile)."""
     from .fused import FusedMatMul, _Ctx
     c = _Ctx(g, order, fed, fetch_refs, device, opts)
+    mask_of = _causal_mask if os.environ.get("TFSERVE_GEMMA", "1") == "0" else _window_mask
     for name in list(order):
         out = g.nodes.get(name)
         if out is None or out.op != "Reshape":
             continue
-        core = _causal_core(g, out)
+        core = _causal_core(g, out, mask_of)
         if core is None:
             continue
-        qk, pv, S, scale, closed, adder_ref, interior = core
+        qk, pv, S, scale, closed, adder_ref, interior, window = core
         rq, rk = _rope_of(g, qk.inputs[0]), _rope_of(g, qk.inputs[1])
         if rq is None or rk is None or not torch.equal(rq[1], rk[1]) or not torch.equal(rq[2], rk[2]):
             continue
@@ -1320,7 +1371,8 @@ def fuse_rope_attention(g, order, fed, fetch_refs, device, opts):
         out.op = "_RopeGQAttention"
         out.inputs = [(qkv_name, 0)] + ([adder_ref] if adder_ref is not None else [])
         out.ctrl = []
-        out.attrs = {"_impl": RopeGQAttentionOp(H, K, D, S, scale, closed, rq[1], rq[2], device, c.use_hip, qk_norm)}
+        out.attrs = {"_impl": RopeGQAttentionOp(H, K, D, S, scale, closed, rq[1], rq[2], device, c.use_hip, qk_norm,
+                                                window)}
         c.refresh()
 
 
@@ -1413,10 +1465,11 @@ class RopeAttentionOp:
 
 class GeGLUOp:
     """gelu_erf(gu[:, :F]) * gu[:, F:] after one GEMM over [W_gate | W_up]: ``geglu``
-    (kernels/llama.hip) on the device for F % 8 == 0, else torch in fp32."""
+    (kernels/llama.hip) on the device for F % 8 == 0, else torch in fp32.  ``approximate``:
+    the gate is the tanh form of the GELU (Gemma), the kernel's second build."""
 
-    def __init__(self, width: int, use_hip: bool):
-        self.f, self.use_hip = width, use_hip
+    def __init__(self, width: int, use_hip: bool, approximate: bool = False):
+        self.f, self.use_hip, self.approximate = width, use_hip, bool(approximate)
 
     def __call__(self, ctx, node, ins):
         gu = O.to_torch(ins[0])
@@ -1426,10 +1479,11 @@ class GeGLUOp:
         if self.use_hip and gu.is_cuda and F_ % 8 == 0:
             from ..ops import hip
             from .fused import _to_bf16
-            y = hip().geglu(_to_bf16(gu).reshape(-1, 2 * F_).contiguous())
+            g2 = _to_bf16(gu).reshape(-1, 2 * F_).contiguous()
+            y = hip().geglu(g2, None, True) if self.approximate else hip().geglu(g2)
             return [y.reshape(list(gu.shape[:-1]) + [F_])]
         gf = gu.float()
-        y = F.gelu(gf[..., :F_]) * gf[..., F_:]
+        y = F.gelu(gf[..., :F_], approximate="tanh" if self.approximate else "none") * gf[..., F_:]
         return [y if not gu.is_cuda else y.to(gu.dtype)]
 
 
@@ -1574,8 +1628,9 @@ def fuse_rope_encoder_attention(g, order, fed, fetch_refs, device, opts):
 def fuse_geglu(g, order, fed, fetch_refs, device, opts):
     """``Mul(gelu_erf(s0), s1)`` (operands in either order) with ``s0, s1 = Split(dense(x), 2,
     axis = -1)`` of one bias-free dense read by nothing else -> ``_FusedMatMul(x; Wi)`` ->
-    ``_GeGLU``.  The GELU is ``match_gelu_subgraph``'s erf form; the tanh form, a
-    biased dense, another axis or an interior node read elsewhere leaves the graph alone."""
+    ``_GeGLU``.  The GELU is ``match_gelu_subgraph``'s erf form or its tanh form (Gemma;
+    the op then carries ``approximate``); a biased dense, another axis or an interior node
+    read elsewhere leaves the graph alone."""
     import types
     from .fused import FusedMatMul, _Ctx
     c = _Ctx(g, order, fed, fetch_refs, device, opts)
@@ -1600,7 +1655,7 @@ def fuse_geglu(g, order, fed, fetch_refs, device, opts):
         view = types.SimpleNamespace(g=g, fetch_nodes=c.fetch_nodes,
                                      cons={**c.cons, sp.name: [e for e in readers if e[2] == 0]})
         m = match_gelu_subgraph(g, view, sp.name)
-        if m is None or m[0] != "gelu_erf" or (m[2].name, 0) != out.inputs[1 - k]:
+        if m is None or m[0] not in ("gelu_erf", "gelu_tanh") or (m[2].name, 0) != out.inputs[1 - k]:
             continue
         interior = m[1] + [m[2], sp] + ds[3]
         if not _interior_ok(c, interior, out):
@@ -1612,7 +1667,7 @@ def fuse_geglu(g, order, fed, fetch_refs, device, opts):
         out.op = "_GeGLU"
         out.inputs = [(mm_name, 0)]
         out.ctrl = []
-        out.attrs = {"_impl": GeGLUOp(int(ds[1].shape[1]) // 2, c.use_hip)}
+        out.attrs = {"_impl": GeGLUOp(int(ds[1].shape[1]) // 2, c.use_hip, m[0] == "gelu_tanh")}
         c.refresh()
 
 

@@ -1223,6 +1223,74 @@ Tensor rope_gqa_attention(const Tensor& qkv, const Tensor& cos, const Tensor& si
   return y;
 }
 
+// 256-wide heads with an optional sliding window (kernels/gqattn256.hip): names of its own, rope_gqa_attention
+// stays at widths 64 and 128
+Tensor rope_gqa_attention256(const Tensor& qkv, const Tensor& cos, const Tensor& sin,
+                             const c10::optional<Tensor>& key_adder, int64_t heads, int64_t kv_heads, double scale,
+                             int64_t window, const c10::optional<Tensor>& out, const c10::optional<Tensor>& q_norm,
+                             const c10::optional<Tensor>& k_norm, double norm_eps) {
+  constexpr int64_t D = 256;
+  need(qkv, at::kBFloat16, "qkv");
+  need(cos, at::kFloat, "cos");
+  need(sin, at::kFloat, "sin");
+  TORCH_CHECK(qkv.dim() == 3, "rope_gqa_attention256: qkv must be [B, S, (H + 2*Hkv)*256]");
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(qkv.device());
+  const int64_t B = qkv.size(0), S = qkv.size(1), W = qkv.size(2);
+  TORCH_CHECK(heads >= 1 && kv_heads >= 1 && W == (heads + 2 * kv_heads) * D,
+              "rope_gqa_attention256 kernel supports head_dim 256: qkv width must be (heads + 2*kv_heads)*256, got ", W);
+  TORCH_CHECK(heads % kv_heads == 0 && (heads / kv_heads == 1 || heads / kv_heads == 2 || heads / kv_heads == 4 ||
+                                        heads / kv_heads == 8),
+              "rope_gqa_attention256: heads / kv_heads must be 1, 2, 4 or 8, got ", heads, " / ", kv_heads);
+  TORCH_CHECK(tfsk::rope_gqa_attention256_supported(S, heads, kv_heads), "rope_gqa_attention256 kernel supports 1 <= S <= ",
+              tfsk::kMaxAttentionSeq, ", got S = ", S);
+  TORCH_CHECK(S * W * 2 < (int64_t(1) << 31) && B * kv_heads < (int64_t(1) << 31),
+              "rope_gqa_attention256: one image's qkv rows exceed 2 GiB");
+  TORCH_CHECK(aligned16(qkv), "rope_gqa_attention256: qkv must be 16-byte aligned");
+  TORCH_CHECK(cos.dim() == 2 && cos.size(0) == S && cos.size(1) == D / 2 && sin.dim() == 2 && sin.size(0) == S &&
+                  sin.size(1) == D / 2,
+              "rope_gqa_attention256: cos / sin must be [S, ", D / 2, "]");
+  TORCH_CHECK(cos.device() == qkv.device() && sin.device() == qkv.device(),
+              "rope_gqa_attention256: cos / sin are on another device");
+  TORCH_CHECK(aligned16(cos) && aligned16(sin), "rope_gqa_attention256: cos / sin must be 16-byte aligned");
+  const float* ap = nullptr;
+  int64_t bstride = 0;
+  if (key_adder.has_value()) {
+    need(*key_adder, at::kFloat, "key_adder");
+    TORCH_CHECK(key_adder->dim() == 2 && key_adder->size(1) == S && (key_adder->size(0) == B || key_adder->size(0) == 1),
+                "rope_gqa_attention256: key_adder must be [B, S] or [1, S]");
+    TORCH_CHECK(key_adder->device() == qkv.device(), "rope_gqa_attention256: key_adder is on another device");
+    bstride = key_adder->size(0) == 1 ? 0 : S;
+    ap = key_adder->data_ptr<float>();
+  }
+  Tensor y = out.has_value() ? *out : torch::empty({B, S, heads * D}, qkv.options());
+  need(y, at::kBFloat16, "out");
+  TORCH_CHECK(y.device() == qkv.device() && y.numel() == B * S * heads * D,
+              "rope_gqa_attention256: out has the wrong size");
+  TORCH_CHECK(aligned16(y), "rope_gqa_attention256: out must be 16-byte aligned");
+  const float *qg = nullptr, *kg = nullptr;
+  TORCH_CHECK(q_norm.has_value() == k_norm.has_value(), "rope_gqa_attention256: q_norm and k_norm go together");
+  if (q_norm.has_value()) {
+    need(*q_norm, at::kFloat, "q_norm");
+    need(*k_norm, at::kFloat, "k_norm");
+    TORCH_CHECK(q_norm->dim() == 1 && q_norm->size(0) == D && k_norm->dim() == 1 && k_norm->size(0) == D,
+                "rope_gqa_attention256: q_norm / k_norm must be [", D, "]");
+    TORCH_CHECK(q_norm->device() == qkv.device() && k_norm->device() == qkv.device(),
+                "rope_gqa_attention256: q_norm / k_norm are on another device");
+    TORCH_CHECK(aligned16(*q_norm) && aligned16(*k_norm),
+                "rope_gqa_attention256: q_norm / k_norm must be 16-byte aligned");
+    TORCH_CHECK(norm_eps > 0.0, "rope_gqa_attention256: norm_eps must be > 0 with a qk norm, got ", norm_eps);
+    qg = q_norm->data_ptr<float>();
+    kg = k_norm->data_ptr<float>();
+  }
+  // any int is a window: one that reaches key 0 from the last row says the same as none
+  const int w = window < 0 || window >= S - 1 ? -1 : int(window);
+  check(tfsk::rope_gqa_attention256_launch(bf16p(qkv), cos.data_ptr<float>(), sin.data_ptr<float>(), ap, bf16p_mut(y),
+                                           int(B), int(S), int(heads), int(kv_heads), float(scale), w, bstride,
+                                           cur_stream(qkv), qg, kg, float(norm_eps)),
+        "rope_gqa_attention256");
+  return y;
+}
+
 Tensor rope_attention(const Tensor& qkv, const Tensor& cos, const Tensor& sin, const c10::optional<Tensor>& key_adder,
                       int64_t heads, double scale, int64_t window, const c10::optional<Tensor>& out) {
   need(qkv, at::kBFloat16, "qkv");
@@ -1315,7 +1383,7 @@ Tensor swiglu(const Tensor& gu, const c10::optional<Tensor>& out) {
   return y;
 }
 
-Tensor geglu(const Tensor& gu, const c10::optional<Tensor>& out) {
+Tensor geglu(const Tensor& gu, const c10::optional<Tensor>& out, bool approximate) {
   need(gu, at::kBFloat16, "gu");
   TORCH_CHECK(gu.dim() == 2 && gu.size(1) >= 16 && gu.size(1) % 16 == 0, "geglu: gu must be [M, 2F] with F % 8 == 0");
   c10::hip::HIPGuardMasqueradingAsCUDA guard(gu.device());
@@ -1324,7 +1392,7 @@ Tensor geglu(const Tensor& gu, const c10::optional<Tensor>& out) {
   need(y, at::kBFloat16, "out");
   TORCH_CHECK(y.numel() == M * F && y.device() == gu.device(), "geglu: out has the wrong size");
   TORCH_CHECK(aligned16(gu) && aligned16(y), "geglu: tensors must be 16-byte aligned");
-  check(tfsk::geglu_launch(bf16p(gu), bf16p_mut(y), M, int(F), cur_stream(gu)), "geglu");
+  check(tfsk::geglu_launch(bf16p(gu), bf16p_mut(y), M, int(F), cur_stream(gu), approximate), "geglu");
   return y;
 }
 
@@ -1684,8 +1752,22 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           return tfsk::rope_attention_supported(S, D, heads, window);
         }, py::arg("S"), py::arg("D"), py::arg("heads"), py::arg("window") = -1,
         "whether rope_attention takes length S with heads of width D and this window");
-  m.def("geglu", &geglu, py::arg("gu"), py::arg("out") = py::none(),
-        "bf16(gelu_erf(gu[:, :F]) * gu[:, F:]) for gu [M, 2F] bf16, F % 8 == 0");
+  m.def("geglu", &geglu, py::arg("gu"), py::arg("out") = py::none(), py::arg("approximate") = false,
+        "bf16(gelu_erf(gu[:, :F]) * gu[:, F:]) for gu [M, 2F] bf16, F % 8 == 0; approximate: the tanh form of the gate");
+  m.def("rope_gqa_attention256", &rope_gqa_attention256, py::arg("qkv"), py::arg("cos"), py::arg("sin"),
+        py::arg("key_adder") = py::none(), py::arg("heads"), py::arg("kv_heads"), py::arg("scale"),
+        py::arg("window") = -1, py::arg("out") = py::none(), py::arg("q_norm") = py::none(),
+        py::arg("k_norm") = py::none(), py::arg("norm_eps") = 0.0,
+        "causal grouped-query attention over packed qkv [B, S, (H + 2*Hkv)*256] (Q | K | V heads) with a sliding "
+        "window: q and k are rotated by position with the rotate-half tables cos / sin f32 [S, 128] while they are "
+        "loaded, query head h reads K / V head h / (H / Hkv), H / Hkv in {1, 2, 4, 8}; key j is open for query i iff "
+        "0 <= i - j <= window, window < 0 (or >= S - 1) is plain causal; key_adder an optional f32 [B, S] | [1, S]; "
+        "with q_norm / k_norm (f32 [256]) each head's q and k row is RMS-normalised with norm_eps before the rotation");
+  m.def("rope_gqa_attention256_supported",
+        [](int64_t S, int64_t heads, int64_t kv_heads) {
+          return tfsk::rope_gqa_attention256_supported(S, heads, kv_heads);
+        }, py::arg("S"), py::arg("heads"), py::arg("kv_heads"),
+        "whether rope_gqa_attention256 takes length S with heads in groups of heads / kv_heads");
   m.def("rmsnorm", &rmsnorm, py::arg("x"), py::arg("gamma"), py::arg("eps"), py::arg("residual") = py::none(),
         py::arg("out") = py::none(), py::arg("sum_out") = py::none(),
         "bf16((x + residual) * rsqrt(mean((x + residual)^2) + eps) * gamma) over the last dim (C % 8 == 0), the row in "

@@ -386,6 +386,23 @@ hipError_t rope_gqa_attention128_launch(const uint16_t* qkv, const float* cos_t,
                                         const float* q_gamma = nullptr, const float* k_gamma = nullptr,
                                         float eps = 0.f);
 
+// The same operation for 256-wide heads with an optional sliding window (kernels/gqattn256.hip;
+// Gemma-2 / Gemma-3): qkv [B][S][(H + 2*Hkv)*256] bf16, cos / sin f32 [S][128], pairs (i, i + 128).
+// Key j is open for query i iff 0 <= i - j <= window; window < 0 or window >= S - 1 is plain causal
+// and takes a build with no window arithmetic in it.  Closed keys weigh exactly 0.  QK-norm as above
+// with gammas f32 [256].  1 <= S <= kMaxAttentionSeq, H / Hkv in {1, 2, 4, 8}; qkv, ctx, the tables
+// and the gammas 16-B aligned, one image's qkv rows below 2 GiB, both gammas or neither, eps > 0
+// with a norm.  Anything else is hipErrorInvalidValue and launches nothing.
+constexpr bool rope_gqa_attention256_supported(int64_t S, int64_t H, int64_t Hkv) {
+  return S >= 1 && S <= kMaxAttentionSeq && Hkv >= 1 && H >= Hkv && H % Hkv == 0 &&
+         (H / Hkv == 1 || H / Hkv == 2 || H / Hkv == 4 || H / Hkv == 8);
+}
+hipError_t rope_gqa_attention256_launch(const uint16_t* qkv, const float* cos_t, const float* sin_t,
+                                        const float* key_adder, uint16_t* ctx, int B, int S, int H, int Hkv,
+                                        float scale, int window, long adder_bstride, hipStream_t stream,
+                                        const float* q_gamma = nullptr, const float* k_gamma = nullptr,
+                                        float eps = 0.f);
+
 // Bidirectional attention with rotary embedding at load and an optional local window
 // (kernels/rattn.hip): qkv [B][S][3*H*64] bf16 (Q heads | K heads | V heads), cos / sin f32 [S][32]
 // as above, q and k rotated in fp32 and rounded to bf16 once, then
@@ -410,7 +427,8 @@ hipError_t rmsnorm_launch(const uint16_t* x, const uint16_t* r, const float* gam
 // SwiGLU (kernels/llama.hip): y[m][f] = bf16(swish(gu[m][f]) * gu[m][F + f]) in fp32, gu [M][2F], F % 8 == 0.
 hipError_t swiglu_launch(const uint16_t* gu, uint16_t* y, long M, int F, hipStream_t stream);
 // GeGLU (kernels/llama.hip): y[m][f] = bf16(gelu_erf(gu[m][f]) * gu[m][F + f]) in fp32; shapes and rejections as swiglu_launch.
-hipError_t geglu_launch(const uint16_t* gu, uint16_t* y, long M, int F, hipStream_t stream);
+// approximate: the gate is the tanh form 0.5 g (1 + tanh(sqrt(2/pi) (g + 0.044715 g^3))) (Gemma).
+hipError_t geglu_launch(const uint16_t* gu, uint16_t* y, long M, int F, hipStream_t stream, bool approximate = false);
 
 // Windowed attention (Swin) over a packed QKV buffer [R][3*H*32] (bf16):
 // out[row, h, :] = softmax(Q K^T * scale + bias[h] (+ mask[w])) V within each

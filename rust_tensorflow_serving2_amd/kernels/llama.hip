@@ -18,7 +18,10 @@
 //
 // geglu: the same launch with the gate's activation the erf GELU,
 // y[m][f] = bf16(0.5 g (1 + erf(g / sqrt 2)) * u), spelled as the GEMM epilogues
-// spell it (common.h kActGeluErf).
+// spell it (common.h kActGeluErf).  Its tanh-approximate form (Gemma's
+// gelu_pytorch_tanh) is a second compile-time build of the same kernel with
+// common.h's gelu_tanh, 0.5 g (1 + tanh(sqrt(2/pi) (g + 0.044715 g^3))) * u;
+// the erf build is untouched by it.
 
 #include "common.h"
 #include "launch.h"
@@ -196,8 +199,8 @@ hipError_t swiglu_launch(const uint16_t* gu, uint16_t* y, long M, int F, hipStre
   return glu_run<kActSwish>(gu, y, M, F, s);
 }
 
-hipError_t geglu_launch(const uint16_t* gu, uint16_t* y, long M, int F, hipStream_t s) {
-  return glu_run<kActGeluErf>(gu, y, M, F, s);
+hipError_t geglu_launch(const uint16_t* gu, uint16_t* y, long M, int F, hipStream_t s, bool approximate) {
+  return approximate ? glu_run<kActGeluTanh>(gu, y, M, F, s) : glu_run<kActGeluErf>(gu, y, M, F, s);
 }
 
 }  // namespace tfsk

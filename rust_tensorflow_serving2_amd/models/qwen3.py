@@ -44,9 +44,13 @@ def _reshape(g, x, shape, name):
     return g.node("Reshape", name, [x, g.const(name + "/shape", np.array(shape, np.int32))], T=F32)
 
 
-def attention_core(g, x, C, S, nH, nKV, rng, adder, tables, miss="", const_weights=False):
-    """q / k / v denses on x [B * S, C] -> the context [B * S, nH * 128] (before o_proj)."""
-    D = HEAD_DIM
+def attention_core(g, x, C, S, nH, nKV, rng, adder, tables, miss="", const_weights=False, head_dim=HEAD_DIM,
+                   band=None, select=False):
+    """q / k / v denses on x [B * S, C] -> the context [B * S, nH * head_dim] (before o_proj).  ``band``: the
+    0 / 1 matrix [S, S] of open keys (default: the lower triangle; models/gemma3.py passes a sliding window);
+    ``select``: the mask spelled ``SelectV2(band, w, -fill)`` instead of ``w * band - fill * (1 - band)``."""
+    D = head_dim
+    band = np.tril(np.ones((S, S), np.float32)) if band is None else np.asarray(band, np.float32).reshape(S, S)
     if miss and miss not in MISSES:
         raise ValueError(f"unknown miss {miss!r}: one of {MISSES}")
     std = math.sqrt(QKV_GAIN / C)
@@ -74,10 +78,14 @@ def attention_core(g, x, C, S, nH, nKV, rng, adder, tables, miss="", const_weigh
     v = _heads(g, v, S, nH, nKV, "value", head_dim=D)
     w = g.node("BatchMatMulV2", "MatMul", [q, k], T=F32, adj_x=False, adj_y=True)
     w = g.node("Mul", "mul", [w, _c(g, "mul/y", 1.0 / math.sqrt(D))], T=F32)
-    b = g.const("band", np.tril(np.ones((1, 1, S, S), np.float32)))
-    one_minus = g.node("Sub", "sub", [_c(g, "sub/x", 1.0), b], T=F32)
-    fill = g.node("Mul", "mul_2", [_c(g, "mul_2/x", MASK_FILL), one_minus], T=F32)
-    w = g.node("Sub", "sub_1", [g.node("Mul", "mul_1", [w, b], T=F32), fill], T=F32)
+    if select:
+        w = g.node("SelectV2", "SelectV2", [g.const("band", band[None, None] > 0), w, _c(g, "SelectV2/e", -MASK_FILL)],
+                   T=F32)
+    else:
+        b = g.const("band", band[None, None])
+        one_minus = g.node("Sub", "sub", [_c(g, "sub/x", 1.0), b], T=F32)
+        fill = g.node("Mul", "mul_2", [_c(g, "mul_2/x", MASK_FILL), one_minus], T=F32)
+        w = g.node("Sub", "sub_1", [g.node("Mul", "mul_1", [w, b], T=F32), fill], T=F32)
     if adder is not None:
         w = g.node("AddV2", "add", [w, adder], T=F32)
     p = g.node("Softmax", "Softmax", [w], T=F32)

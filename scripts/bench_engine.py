@@ -20,7 +20,7 @@ def main():
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--baseline", action="store_true")
     ap.add_argument("--model", default="resnet50", choices=["resnet50", "resnet50-v2", "resnext50", "mobilenet-v1", "mobilenet-v2", "mobilenet-v3-large",
-                                                      "mobilenet-v3-small", "efficientnet-b0", "convnext-tiny", "vit-b16", "swin-tiny", "bert-base", "modernbert-base", "qwen3-0.6b"])
+                                                      "mobilenet-v3-small", "efficientnet-b0", "convnext-tiny", "vit-b16", "swin-tiny", "bert-base", "modernbert-base", "qwen3-0.6b", "gemma3-1b"])
     ap.add_argument("--graph-tune", type=int, default=1, help="whole-graph tile re-tuning at capture (0 = off)")
     ap.add_argument("--windows", type=int, default=1,
                     help="timed windows of --iters replays each; above 1, graph_ms is their median and "
@@ -58,6 +58,15 @@ def main():
         # 28 layers of GEMMs (q 2048, k and v 1024 each, o 2048 x 1024, gate / up / down 3072) over S = 1024 rows
         # + causal attention over 16 heads of 128 (half the S x S square)
         flop_per_item = 2 * 28 * 1024 * (2 * 2048 + 2 * 1024 + 3 * 3072) * 1024 + 2 * 28 * 2048 * 1024 * 1024
+    elif args.model == "gemma3-1b":
+        from rust_tensorflow_serving2_amd.models import gemma3
+        if not args.model_dir:
+            gemma3.export(path, "gemma3_1b", seed=0)
+        s = Servable("gemma3", 1, path, opts)
+        r = s.runner("serving_default", ["input_ids", "input_mask"], ["logits", "hidden"])
+        # 26 layers of GEMMs (q 1024, k and v 256 each, o 1024 x 1152, gate / up / down 6912) over S = 1024 rows
+        # + attention over 4 heads of 256: 4 global layers (half the S x S square), 22 local ones (512 keys a row)
+        flop_per_item = 2 * 26 * 1152 * (2 * 1024 + 2 * 256 + 3 * 6912) * 1024 + 4 * 1024 * 1024 * (4 * 512 + 22 * 512)
     elif args.model.startswith("mobilenet"):
         from rust_tensorflow_serving2_amd.models import mobilenet
         if not args.model_dir:
@@ -115,7 +124,7 @@ def main():
                  np.zeros((b, 128), np.int32)]
         elif args.model == "modernbert-base":
             x = [rng.integers(0, 50368, (b, 1024)).astype(np.int32), np.ones((b, 1024), np.int32)]
-        elif args.model == "qwen3-0.6b":
+        elif args.model in ("qwen3-0.6b", "gemma3-1b"):
             x = [rng.integers(0, 32000, (b, 1024)).astype(np.int32), np.ones((b, 1024), np.int32)]
         else:
             x = [rng.random((b, 224, 224, 3), dtype=np.float32)]

@@ -23,7 +23,11 @@ repeated for their groups.  ``--d128`` runs the D = 128 shape list.  ``--qk-norm
 (D = 128 shapes) gives the kernel a QK-norm and times it against the op's torch
 path, the norm-less kernel and two rmsnorm launches plus the norm-less kernel.
 
-    python scripts/gqattn_bench.py [--shapes B,S,H,Hkv[,D] ...] [--d128] [--qk-norm] [--reps 21] [--rounds 5] [--json]
+A shape with D = 256 and a sixth field, the window, runs kernels/gqattn256.hip
+(rope_gqa_attention256) with a QK-norm against the same two baselines; sdpa takes
+no norm and gets a window as a boolean mask.  ``--d256`` runs Gemma's shape list.
+
+    python scripts/gqattn_bench.py [--shapes B,S,H,Hkv[,D[,window]] ...] [--d128] [--d256] [--qk-norm] [--reps 21] [--rounds 5] [--json]
 """
 import argparse
 import json
@@ -38,6 +42,8 @@ from dwconv_bench import timed  # noqa: E402
 
 SHAPES = [(b, s, 32, k) for k in (8, 4) for s in (128, 512, 1024, 2048) for b in (1, 8)]
 SHAPES_D128 = [(b, s, 32, k, 128) for k in (8, 32) for s in (128, 512, 1024, 2048) for b in (1, 8)]
+SHAPES_D256 = [(b, s, h, k, 256, w) for h, k in ((4, 1), (8, 4)) for s in (512, 1024, 2048, 4096) for b in (1, 8)
+               for w in (-1, 511)]
 
 
 def parse(text):
@@ -77,6 +83,33 @@ def sdpa(qkv, cos, sin, h, k, d, scale, out):
     v = v.reshape(b, s, k, d).repeat_interleave(h // k, 2).transpose(1, 2)
     y = torch.nn.functional.scaled_dot_product_attention(q, kk, v, is_causal=True, scale=scale)
     out.copy_(y.transpose(1, 2).reshape(b, s, h * d))
+
+
+def candidates256(H, qkv, cos, sin, h, k, window, out, qk_norm):
+    """D = 256 (kernels/gqattn256.hip): the kernel with the QK-norm and this window, the op's torch path doing the
+    same, and torch rotation + sdpa (no norm; a window goes in as a boolean mask, which costs sdpa its causal path)."""
+    from rust_tensorflow_serving2_amd.graph.patterns import RopeGQAttentionOp
+    d, (b, s, _) = 256, qkv.shape
+    scale = d ** -0.5
+    op = RopeGQAttentionOp(h, k, d, s, scale, -10000.0, cos, sin, qkv.device, False, qk_norm, window)
+    flat = qkv.reshape(b * s, -1)
+    band = None
+    if 0 <= window < s - 1:
+        i = torch.arange(s, device=qkv.device)
+        band = ((i[:, None] - i[None, :]) >= 0) & ((i[:, None] - i[None, :]) <= window)
+
+    def torch_sdpa():
+        q, kk, v = qkv.split([h * d, k * d, k * d], -1)
+        q = rotated(q, h, d, cos, sin).transpose(1, 2)
+        kk = rotated(kk, k, d, cos, sin).repeat_interleave(h // k, 2).transpose(1, 2)
+        v = v.reshape(b, s, k, d).repeat_interleave(h // k, 2).transpose(1, 2)
+        y = torch.nn.functional.scaled_dot_product_attention(q, kk, v, attn_mask=band, is_causal=band is None,
+                                                             scale=scale)
+        out["torch sdpa"].copy_(y.transpose(1, 2).reshape(b, s, h * d))
+    return {"rope_gqa": lambda: H.rope_gqa_attention256(qkv, cos, sin, None, h, k, scale, window, out["rope_gqa"],
+                                                        *qk_norm),
+            "op torch path": lambda: out["op torch path"].copy_(op(None, None, [flat])[0].reshape(b, s, h * d)),
+            "torch sdpa": torch_sdpa}
 
 
 def candidates(H, qkv, cos, sin, h, k, d, out, qk_norm=None):
@@ -122,6 +155,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shapes", nargs="+", type=parse, default=None, metavar="B,S,H,Hkv[,D]")
     ap.add_argument("--d128", action="store_true", help="the D = 128 shape list instead of the D = 64 one")
+    ap.add_argument("--d256", action="store_true", help="the D = 256 shape list (Gemma: QK-norm, window -1 and 511)")
     ap.add_argument("--qk-norm", action="store_true",
                     help="D = 128 with the QK-norm in the kernel, against the op's torch path, the norm-less kernel "
                          "(the cost of the norm) and two rmsnorm launches followed by the norm-less kernel")
@@ -136,7 +170,7 @@ def main():
     H = ops.hip()
     dev = torch.device("cuda:0")
     flush = ops._flush_buffer()
-    for shape in args.shapes or (SHAPES_D128 if args.d128 else SHAPES):
+    for shape in args.shapes or (SHAPES_D256 if args.d256 else SHAPES_D128 if args.d128 else SHAPES):
         b, s, h, k = shape[:4]
         d = shape[4] if len(shape) > 4 else 64
         g = torch.Generator().manual_seed(s * 100 + b)
@@ -149,8 +183,13 @@ def main():
                 raise SystemExit("--qk-norm needs D = 128 shapes")
             names = ["rope_gqa", "op torch path", "no norm", "rmsnorm x2 + no norm"]
             qk_norm = tuple((1 + 0.25 * torch.randn(d, generator=g)).to(dev) for _ in range(2)) + (1e-6,)
+        window = shape[5] if len(shape) > 5 else -1
+        if d == 256:
+            names = ["rope_gqa", "op torch path", "torch sdpa"]
+            qk_norm = tuple((1 + 0.25 * torch.randn(d, generator=g)).to(dev) for _ in range(2)) + (1e-6,)
         out = {n: torch.empty(b, s, h * d, dtype=torch.bfloat16, device=dev) for n in names}
-        runs = candidates(H, qkv, cos, sin, h, k, d, out, qk_norm)
+        runs = candidates256(H, qkv, cos, sin, h, k, window, out, qk_norm) if d == 256 else \
+            candidates(H, qkv, cos, sin, h, k, d, out, qk_norm)
         rounds = {n: [] for n in runs}
         for _ in range(args.rounds):
             for n, fn in runs.items():                       # alternating: every round times every candidate once
@@ -162,7 +201,8 @@ def main():
         spread = {n: (max(v) - min(v)) / med[n] for n, v in rounds.items()}
         cells = " ".join(f"{n} {med[n]:.1f} us (spread {spread[n]:.1%})" for n in names)
         ratios = " ".join(f"{n} / rope_gqa {med[n] / med['rope_gqa']:.2f}" for n in names[1:])
-        print(f"{f'{b}x{s}x{h}/{k} D={d}':>22}  {cells}  {ratios}", flush=True)
+        tag = f"{b}x{s}x{h}/{k} D={d}" + (f" w={window}" if d == 256 else "")
+        print(f"{tag:>22}  {cells}  {ratios}", flush=True)
         if args.json:
             print(json.dumps({"b": b, "s": s, "h": h, "hkv": k, "d": d, "rounds": args.rounds,
                               "us": {n: [round(x, 2) for x in v] for n, v in rounds.items()}}), flush=True)

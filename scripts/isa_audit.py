@@ -172,10 +172,14 @@ def resources(asm: str):
     return out
 
 
-def print_resources(files, only):
+def print_resources(files, only, as_built=False):
     extra = ["-munsafe-fp-atomics"]          # as _build.build_hip compiles them
+    own = {}
+    if as_built:                             # ... and with the flags _build.SOURCE_FLAGS gives single sources
+        sys.path.insert(0, ROOT)
+        from rust_tensorflow_serving2_amd._build import SOURCE_FLAGS as own
     with cf.ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 1)) as ex:
-        asms = list(ex.map(lambda s: compile_asm(s, extra), files))
+        asms = list(ex.map(lambda s: compile_asm(s, extra + own.get(os.path.basename(s), [])), files))
     print("file symbol " + " ".join(RES_COLS) + " code")
     for src, asm in zip(files, asms):
         for sym, r in sorted(resources(asm).items()):
@@ -192,10 +196,13 @@ def main():
     ap.add_argument("--resources", action="store_true",
                     help="print each kernel's registers, spills, scratch, LDS, occupancy, code bytes and MFMA count "
                          "(one line per symbol: diff two trees' tables) instead of the stall scan")
+    ap.add_argument("--as-built", action="store_true",
+                    help="with --resources: add the per-source flags of _build.SOURCE_FLAGS (e.g. -packed-fp32-ops), "
+                         "so the table is the shipped build's; without it every source gets the common flags only")
     a = ap.parse_args()
     files = [f if os.path.isabs(f) else os.path.join(KDIR, f) for f in a.files] or sorted(glob.glob(f"{KDIR}/*.hip"))
     if a.resources:
-        return print_resources(files, a.kernel)
+        return print_resources(files, a.kernel, a.as_built)
     for src in files:
         asm = compile_asm(src)
         for sym, body in kernels(asm):

@@ -28,6 +28,9 @@ same ``<root>/<name>/<version>/`` layout:
 * ``qwen3`` (= ``qwen3_0_6b``) / ``qwen3_tiny``  Qwen3-style decoder: Llama's graph with 128-wide heads whose total width is not the
                     hidden width and a per-head RMSNorm on q and k before the rotation; 1024 wide, 28 layers, 16 / 8 heads,
                     SwiGLU 3072, S = 1024, vocabulary 32000, and a 2-layer, 256-wide one (4 / 2 heads) at S = 160
+* ``gemma3`` (= ``gemma3_1b``) / ``gemma3_tiny``  Gemma-3-style decoder: 256-wide heads with QK-norm, five local layers (sliding window
+                    512, rope theta 1e4) to one global, sandwich norms, tanh GeGLU; 1152 wide, 26 layers, 4 / 1 heads, MLP 6912,
+                    S = 1024, vocabulary 32000, and a 3-layer, 128-wide one (window 49, one global layer) at S = 160
 * ``modernbert`` (= ``modernbert_base`` and ``modernbert_tiny``)  ModernBERT-style encoder, 768 wide, 22 layers, 12 heads, GeGLU 1152,
                     S = 1024, vocabulary 50368 (pre-norm, bias-free, rotate-half RoPE in every layer, two layers in three
                     local with a +-64 band adder; input_ids / input_mask -> hidden, cls) and a 3-layer, 128-wide one at
@@ -96,6 +99,9 @@ def main(argv=None):
         elif m in ("qwen3", "qwen3_0_6b", "qwen3_tiny"):
             from rust_tensorflow_serving2_amd.models import qwen3
             qwen3.export(out, "qwen3_0_6b" if m == "qwen3" else m, seed=args.seed)
+        elif m in ("gemma3", "gemma3_1b", "gemma3_tiny"):
+            from rust_tensorflow_serving2_amd.models import gemma3
+            gemma3.export(out, "gemma3_1b" if m == "gemma3" else m, seed=args.seed)
         elif m in ("modernbert_base", "modernbert_tiny"):
             from rust_tensorflow_serving2_amd.models import modernbert
             modernbert.export(out, m, seed=args.seed)
