@@ -63,10 +63,11 @@ def _local_includes(src, headers):
 
 # Flags of single sources, by file name.  cattn.hip: no packed-fp32 VALU ops
 # (the compiler pairs the softmax's scalar fp32 arithmetic otherwise); gqattn.hip
-# gqattn128.hip, gqattn256.hip and rattn.hip have the same softmax and llama.hip is elementwise fp32 throughout.
+# gqattn128.hip, gqattn256.hip, rattn.hip and battn.hip have the same softmax and llama.hip is elementwise fp32 throughout.
 _NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 SOURCE_FLAGS = {"cattn.hip": _NO_PACKED_FP32, "gqattn.hip": _NO_PACKED_FP32, "gqattn128.hip": _NO_PACKED_FP32,
-                "gqattn256.hip": _NO_PACKED_FP32, "rattn.hip": _NO_PACKED_FP32, "llama.hip": _NO_PACKED_FP32}
+                "gqattn256.hip": _NO_PACKED_FP32, "rattn.hip": _NO_PACKED_FP32, "battn.hip": _NO_PACKED_FP32,
+                "llama.hip": _NO_PACKED_FP32}
 
 
 def _compile_all(compiler, sources, headers, flags, tag, jobs):

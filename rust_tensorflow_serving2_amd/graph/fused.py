@@ -1127,7 +1127,7 @@ def _impl_op(ctx, node, ins):
 for _op in ("_FusedConv2D", "_FusedDepthwiseConv2D", "_FusedDepthwiseLN", "_FusedGroupedConv2D", "_FusedDualConv", "_FusedMatMul", "_GlobalAvgPool", "_MaxPool",
             "_SqueezeExcite", "_SqueezeExciteSigmoid",
             "_SoftmaxArgMax", "_LayerNorm",
-            "_FusedQKV", "_Attention", "_CausalAttention", "_RopeGQAttention", "_RopeAttention", "_RMSNorm", "_SwiGLU", "_GeGLU", "_WindowAttention", "_EmbeddingLN", "_KeyMaskAdder", "_DenseSoftmax", "_PatchTokens",
+            "_FusedQKV", "_Attention", "_CausalAttention", "_RopeGQAttention", "_RopeAttention", "_BiasAttention", "_RMSNorm", "_SwiGLU", "_GeGLU", "_WindowAttention", "_EmbeddingLN", "_KeyMaskAdder", "_DenseSoftmax", "_PatchTokens",
             "_EmbeddingBag", "_DotInteraction"):
     O.OPS[_op] = _impl_op
 

@@ -28,6 +28,10 @@
   ``gelu_erf(s0) * s1`` over the two halves of one dense
         => _FusedQKV(x) -> _RopeAttention(qkv, key_adder; window)   _FusedMatMul -> _GeGLU
 
+* T5's encoder attention (``fuse_bias_attention``): the bidirectional core with one constant per-head bias that is
+  exactly Toeplitz (a function of j - i: the relative-position bias) and an optional adder, in either nesting
+        => _FusedQKV(x) -> _BiasAttention(qkv, key_adder; table [H, 2 S - 1])
+
 * Swin's windowed attention (``fuse_window_attention``) and the roll / partition /
   reverse layout around it (``fold_window_layout``)
         => _FusedQKV(x)  ->  _WindowAttention(qkv; bias, mask, grid)
@@ -1671,6 +1675,195 @@ def fuse_geglu(g, order, fed, fetch_refs, device, opts):
         c.refresh()
 
 
+# ------------------------------------------------------------------ T5: attention with a relative-position bias
+class BiasAttentionOp:
+    """Bidirectional attention over a packed [Q heads | K heads | V heads] buffer with a
+    per-head bias that depends on j - i only: ``table`` [H, 2 S - 1], entry j - i + S - 1
+    (T5's relative-position bias; any exactly Toeplitz [H, S, S] constant).  Inputs
+    ``[qkv, adder?]``.
+
+    On the device, for D = 64, S within range and an adder that is absent or
+    [B | 1, 1, 1, S], one ``bias_attention`` launch (kernels/battn.hip; docs/numerics.md,
+    "Relative-bias attention").  Anywhere else the graph's own arithmetic with torch, in
+    fp32: the dense [H, S, S] bias rebuilt from the table by indexing, which is the
+    matched constant bit for bit, added to the scores before the adder, or summed with
+    the adder first (``sum_first``) where the graph shares that sum between its layers."""
+
+    def __init__(self, heads, head_dim, seq, scale, table, device, use_hip, sum_first=False):
+        self.h, self.d, self.s = heads, head_dim, seq
+        self.scale, self.use_hip, self.sum_first = scale, use_hip, bool(sum_first)
+        self.table = to_device(table.float().contiguous(), device)
+
+    def dense_bias(self, device) -> torch.Tensor:
+        """[1, H, S, S] f32: table[h, j - i + S - 1]."""
+        pos = torch.arange(self.s, device=device)
+        return self.table.to(device)[:, pos[None, :] - pos[:, None] + (self.s - 1)][None]
+
+    def __call__(self, ctx, node, ins):
+        qkv = O.to_torch(ins[0])
+        adder = O.to_torch(ins[1]) if len(ins) > 1 else None
+        S, H, D = self.s, self.h, self.d
+        W = 3 * H * D
+        if qkv.numel() % (S * W):
+            raise O.OpError(f"{node.name}: {list(qkv.shape)} is not [B * {S}, {W}]")
+        B = qkv.numel() // (S * W)
+        key_adder = adder is None or (adder.dim() == 4 and tuple(adder.shape[1:]) == (1, 1, S) and
+                                      adder.shape[0] in (1, B))
+        if self.use_hip and qkv.is_cuda and D == 64 and 1 <= S <= MAX_ATTENTION_SEQ and key_adder:
+            from ..ops import hip
+            from .fused import _to_bf16
+            q3 = _to_bf16(qkv).reshape(B, S, W).contiguous()
+            ka = None if adder is None else adder.float().reshape(-1, S).contiguous().to(qkv.device)
+            y = hip().bias_attention(q3, self.table, ka, H, self.scale)
+            return [y.reshape(B * S, H * D)]
+        q, k, v = qkv.float().reshape(B, S, 3, H, D).permute(2, 0, 3, 1, 4)
+        sc = q @ k.transpose(-1, -2)
+        if self.scale != 1.0:
+            sc = sc * self.scale
+        bias = self.dense_bias(sc.device)
+        if adder is None:
+            sc = sc + bias
+        elif self.sum_first:
+            sc = sc + (bias + adder.float().to(sc.device))
+        else:
+            sc = sc + bias + adder.float().to(sc.device)
+        y = (torch.softmax(sc, -1) @ v).permute(0, 2, 1, 3).reshape(B * S, H * D)
+        return [y if not qkv.is_cuda else y.to(qkv.dtype)]
+
+
+def _head_bias_shaped(v: torch.Tensor) -> bool:
+    """[1, H, S, S] or [H, S, S], by shape."""
+    return v.is_floating_point() and v.dim() in (3, 4) and v.shape[-1] == v.shape[-2] and (v.dim() == 3 or v.shape[0] == 1)
+
+
+def _toeplitz_table(bias: torch.Tensor, H: int, S: int) -> Optional[torch.Tensor]:
+    """bias [1, H, S, S] | [H, S, S] with b[h, i, j] == b[h, i + 1, j + 1] everywhere (compared for
+    equality) -> its diagonals [H, 2 S - 1], entry j - i + S - 1, else None.  Indexing only: a meta
+    constant (a replica that receives its weights) gives a meta table and is taken on its shape, the
+    values having been compared where the weights were read."""
+    if not _head_bias_shaped(bias):
+        return None
+    b = bias[0] if bias.dim() == 4 else bias
+    if tuple(b.shape) != (H, S, S):
+        return None
+    if not b.is_meta and not torch.equal(b[:, :-1, :-1], b[:, 1:, 1:]):
+        return None
+    return torch.cat([b[:, 1:, 0].flip(-1), b[:, 0, :]], -1)
+
+
+def fuse_bias_attention(g, order, fed, fetch_refs, device, opts):
+    """T5's attention core -> _FusedQKV -> _BiasAttention: fuse_attention's skeleton::
+
+        w = BatchMatMul(q, k, adj_y)  [Mul by c | RealDiv by c: _scale_of; T5 has none]
+        scores = (w + bias) + adder   |   w + (bias + adder)          (AddV2, operands in either order)
+        y = Reshape(Transpose(BatchMatMul(Softmax(scores), v), [0, 2, 1, 3]), [-1, H * D])
+
+    with exactly one constant ``bias`` shaped [1, H, S, S] or [H, S, S] that is exactly
+    Toeplitz per head (``_toeplitz_table``) and at most one non-constant ``adder`` (the op
+    takes [B | 1, 1, 1, S] on the device); q, k, v from three denses on one input, with a
+    bias or without.  In the second spelling ``bias + adder`` is computed once and read by
+    every layer: that node is not interior, it is bypassed (the op reads ``adder``) and
+    stays until its last reader is rewritten, after which nothing reaches it.
+
+    Runs directly before fuse_attention.  No earlier pass takes a core with a constant
+    per-head bias (fuse_window_attention needs the window reshapes around it), and what
+    this pass leaves -- a bias that is not Toeplitz, two constants, a per-head constant of
+    another S or H, a per-head bias that is not constant, an interior node read elsewhere
+    -- fuse_attention sees unchanged."""
+    from .fused import FusedMatMul, _Ctx
+    c = _Ctx(g, order, fed, fetch_refs, device, opts)
+    tables = {}                       # bias Const ref -> table | None: the layers share one constant
+    for name in list(order):
+        out = g.nodes.get(name)
+        if out is None or out.op != "Reshape":
+            continue
+        t2 = _node(g, out.inputs[0])
+        if t2 is None or t2.op != "Transpose" or _ints(g, t2.inputs[1]) != [0, 2, 1, 3]:
+            continue
+        pv = _node(g, t2.inputs[0])
+        if pv is None or pv.op not in _BMM or pv.attr("adj_x", False) or pv.attr("adj_y", False):
+            continue
+        sm = _node(g, pv.inputs[0])
+        if sm is None or sm.op != "Softmax":
+            continue
+        interior = [t2, pv, sm]
+        # ---- the adds under the Softmax: one constant (the bias) and at most one other (the adder)
+        cur, biases, adders, ok, sum_first = _node(g, sm.inputs[0]), [], [], True, False
+        while cur is not None and cur.op in ("Add", "AddV2") and len(cur.inputs) == 2:
+            sides = [k for k in (0, 1) if _reaches_qk(g, cur.inputs[k])]
+            if len(sides) != 1:
+                ok = False
+                break
+            other = cur.inputs[1 - sides[0]]
+            if _const_t(g, other) is not None:
+                biases.append(other)
+            else:
+                shared = _node(g, other)          # bias + adder, shared by the layers?
+                parts = None
+                if shared is not None and shared.op in ("Add", "AddV2") and len(shared.inputs) == 2:
+                    for k in (0, 1):
+                        cv = _const_t(g, shared.inputs[k])
+                        if cv is not None and _head_bias_shaped(cv) and _const_t(g, shared.inputs[1 - k]) is None:
+                            parts = (shared.inputs[k], shared.inputs[1 - k])
+                if parts is not None:
+                    biases.append(parts[0])
+                    adders.append(parts[1])
+                    sum_first = True
+                else:
+                    adders.append(other)
+            interior.append(cur)
+            cur = _node(g, cur.inputs[sides[0]])
+        if not ok or len(biases) != 1 or len(adders) > 1:
+            continue
+        adder_ref = adders[0] if adders else None
+        scale = 1.0
+        sv = _scale_of(g, cur) if cur is not None and cur.op in ("Mul", "RealDiv") else None
+        if sv is not None:
+            scale = sv[0]
+            interior.append(cur)
+            cur = _node(g, sv[1])
+        qk = cur
+        if qk is None or qk.op not in _BMM or qk.attr("adj_x", False) or not qk.attr("adj_y", False):
+            continue
+        interior.append(qk)
+        hq, hk, hv = _heads_of(g, c, qk.inputs[0]), _heads_of(g, c, qk.inputs[1]), _heads_of(g, c, pv.inputs[1])
+        if hq is None or hk is None or hv is None or hq[1:4] != hk[1:4] or hq[1:4] != hv[1:4]:
+            continue
+        S, H, D = hq[1:4]
+        fshape = _ints(g, out.inputs[1])
+        if fshape is None or len(fshape) != 2 or fshape[-1] != H * D:
+            continue                  # (the op returns [B * S, H * D])
+        if biases[0] not in tables:
+            tables[biases[0]] = _toeplitz_table(_const_t(g, biases[0]), H, S)
+        table = tables[biases[0]]
+        if table is None or tuple(table.shape) != (H, 2 * S - 1):
+            continue
+        interior += hq[4] + hk[4] + hv[4]
+        if adder_ref is not None and adder_ref[0] in {n.name for n in interior}:
+            continue
+        dq, dk, dv = _dense_src(g, c, hq[0]), _dense_src(g, c, hk[0]), _dense_src(g, c, hv[0])
+        if not (dq and dk and dv and dq[0] == dk[0] == dv[0]) or any(d[1].shape[1] != H * D for d in (dq, dk, dv)):
+            continue
+        qkv_nodes = dq[3] + dk[3] + dv[3]
+        if not _interior_ok(c, interior + qkv_nodes, out):
+            continue
+        w, b = torch.cat([dq[1], dk[1], dv[1]], dim=1), torch.cat([dq[2], dk[2], dv[2]])
+        qkv_name = g.unique_name(out.name + "/fused_qkv")
+        g.add(Node(name=qkv_name, op="_FusedQKV", inputs=[dq[0]],
+                   attrs={"_impl": FusedMatMul(w, b, "none", False, device, c.use_hip, qkv_name)}))
+        _remove(g, interior + qkv_nodes)
+        out.op = "_BiasAttention"
+        out.inputs = [(qkv_name, 0)] + ([adder_ref] if adder_ref is not None else [])
+        out.ctrl = []
+        out.attrs = {"_impl": BiasAttentionOp(H, D, S, scale, table, device, c.use_hip, sum_first)}
+        c.refresh()
+
+
+def t5_passes():
+    """TFSERVE_T5=0 (read at every compile) removes the pass: the engine A/B in one build."""
+    return [] if os.environ.get("TFSERVE_T5", "1") == "0" else [fuse_bias_attention]
+
+
 def modernbert_passes():
     """TFSERVE_MODERNBERT=0 (read at every compile) removes the two passes: the engine A/B in one build."""
     return [] if os.environ.get("TFSERVE_MODERNBERT", "1") == "0" else [fuse_rope_encoder_attention, fuse_geglu]
@@ -2373,7 +2566,7 @@ def dlrm_passes():
 
 def bert_passes():
     return [fuse_layernorm, fuse_rmsnorm, fuse_embedding, fuse_window_attention, fold_window_layout, fuse_rope_attention,
-            fuse_causal_attention, fuse_attention, fuse_key_mask, fuse_swiglu] + modernbert_passes()
+            fuse_causal_attention] + t5_passes() + [fuse_attention, fuse_key_mask, fuse_swiglu] + modernbert_passes()
 
 
 def late_passes():

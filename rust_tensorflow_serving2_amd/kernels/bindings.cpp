@@ -1335,6 +1335,45 @@ Tensor rope_attention(const Tensor& qkv, const Tensor& cos, const Tensor& sin, c
   return y;
 }
 
+Tensor bias_attention(const Tensor& qkv, const Tensor& table, const c10::optional<Tensor>& key_adder, int64_t heads,
+                      double scale, const c10::optional<Tensor>& out) {
+  need(qkv, at::kBFloat16, "qkv");
+  need(table, at::kFloat, "table");
+  TORCH_CHECK(qkv.dim() == 3, "bias_attention: qkv must be [B, S, 3*H*D]");
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(qkv.device());
+  const int64_t B = qkv.size(0), S = qkv.size(1), W = qkv.size(2);
+  TORCH_CHECK(heads >= 1 && W % (3 * heads) == 0, "bias_attention: qkv width must be 3*heads*head_dim");
+  const int64_t D = W / (3 * heads);
+  TORCH_CHECK(D == 64, "bias_attention kernel supports head_dim 64, got ", D);
+  TORCH_CHECK(tfsk::bias_attention_supported(S, D, heads), "bias_attention kernel supports 1 <= S <= ",
+              tfsk::kMaxAttentionSeq, ", got S = ", S);
+  TORCH_CHECK(S * W * 2 < (int64_t(1) << 31) && B * heads < (int64_t(1) << 31),
+              "bias_attention: one image's qkv rows exceed 2 GiB");
+  TORCH_CHECK(aligned16(qkv), "bias_attention: qkv must be 16-byte aligned");
+  TORCH_CHECK(table.dim() == 2 && table.size(0) == heads && table.size(1) == 2 * S - 1,
+              "bias_attention: table must be [heads, 2*S - 1] = [", heads, ", ", 2 * S - 1, "]");
+  TORCH_CHECK(table.device() == qkv.device(), "bias_attention: table is on another device");
+  TORCH_CHECK(heads * (2 * S - 1) * 4 < (int64_t(1) << 31), "bias_attention: the table exceeds 2 GiB");
+  const float* ap = nullptr;
+  int64_t bstride = 0;
+  if (key_adder.has_value()) {
+    need(*key_adder, at::kFloat, "key_adder");
+    TORCH_CHECK(key_adder->dim() == 2 && key_adder->size(1) == S && (key_adder->size(0) == B || key_adder->size(0) == 1),
+                "bias_attention: key_adder must be [B, S] or [1, S]");
+    TORCH_CHECK(key_adder->device() == qkv.device(), "bias_attention: key_adder is on another device");
+    bstride = key_adder->size(0) == 1 ? 0 : S;
+    ap = key_adder->data_ptr<float>();
+  }
+  Tensor y = out.has_value() ? *out : torch::empty({B, S, heads * D}, qkv.options());
+  need(y, at::kBFloat16, "out");
+  TORCH_CHECK(y.device() == qkv.device() && y.numel() == B * S * heads * D, "bias_attention: out has the wrong size");
+  TORCH_CHECK(aligned16(y), "bias_attention: out must be 16-byte aligned");
+  check(tfsk::bias_attention_launch(bf16p(qkv), table.data_ptr<float>(), ap, bf16p_mut(y), int(B), int(S), int(heads),
+                                    int(D), float(scale), bstride, cur_stream(qkv)),
+        "bias_attention");
+  return y;
+}
+
 Tensor rmsnorm(const Tensor& x, const Tensor& gamma, double eps, const c10::optional<Tensor>& residual,
                const c10::optional<Tensor>& out, const c10::optional<Tensor>& sum_out) {
   need(x, at::kBFloat16, "x");
@@ -1752,6 +1791,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           return tfsk::rope_attention_supported(S, D, heads, window);
         }, py::arg("S"), py::arg("D"), py::arg("heads"), py::arg("window") = -1,
         "whether rope_attention takes length S with heads of width D and this window");
+  m.def("bias_attention", &bias_attention, py::arg("qkv"), py::arg("table"), py::arg("key_adder") = py::none(),
+        py::arg("heads"), py::arg("scale"), py::arg("out") = py::none(),
+        "bidirectional attention over packed qkv [B, S, 3*H*64] (Q | K | V heads) with a relative-position bias: "
+        "table f32 [H, 2*S - 1], entry j - i + S - 1 of head h is added to the scaled score of query i and key j "
+        "(T5); key_adder an optional f32 [B, S] | [1, S]");
+  m.def("bias_attention_supported",
+        [](int64_t S, int64_t D, int64_t heads) { return tfsk::bias_attention_supported(S, D, heads); }, py::arg("S"),
+        py::arg("D"), py::arg("heads"), "whether bias_attention takes length S with heads of width D");
   m.def("geglu", &geglu, py::arg("gu"), py::arg("out") = py::none(), py::arg("approximate") = false,
         "bf16(gelu_erf(gu[:, :F]) * gu[:, F:]) for gu [M, 2F] bf16, F % 8 == 0; approximate: the tanh form of the gate");
   m.def("rope_gqa_attention256", &rope_gqa_attention256, py::arg("qkv"), py::arg("cos"), py::arg("sin"),

@@ -419,6 +419,19 @@ hipError_t rope_attention_launch(const uint16_t* qkv, const float* cos_t, const 
                                  uint16_t* ctx, int B, int S, int H, int D, int window, float scale,
                                  long adder_bstride, hipStream_t stream);
 
+// Bidirectional attention with a relative-position bias (kernels/battn.hip; T5-style encoders):
+// qkv [B][S][3*H*64] bf16 (Q heads | K heads | V heads), table f32 [H][2*S - 1], then
+// ctx[b,i,h,:] = softmax_j((q_i k_j^T) * scale + table[h][j - i + S - 1] + key_adder) V: the per-head
+// [S][S] bias of a Toeplitz matrix, given by its 2 S - 1 diagonals.  key_adder as in
+// causal_attention_launch.  D = 64, 1 <= S <= kMaxAttentionSeq; qkv and ctx 16-B aligned, the table and
+// the adder 4-B, one image's qkv rows and the table below 2 GiB.
+// Anything else is hipErrorInvalidValue and launches nothing.
+constexpr bool bias_attention_supported(int64_t S, int64_t D, int64_t H) {
+  return D == 64 && S >= 1 && S <= kMaxAttentionSeq && H >= 1;
+}
+hipError_t bias_attention_launch(const uint16_t* qkv, const float* table, const float* key_adder, uint16_t* ctx, int B,
+                                 int S, int H, int D, float scale, long adder_bstride, hipStream_t stream);
+
 // RMSNorm over the last dim (kernels/llama.hip): y = bf16((x + r) * rsqrt(mean((x + r)^2) + eps) * gamma),
 // the row kept in fp32; r an optional residual (null: none), sum an optional second output bf16(x + r)
 // (null: not stored).  cols % 8 == 0, every pointer 16-B aligned; else hipErrorInvalidValue.

@@ -20,7 +20,7 @@ def main():
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--baseline", action="store_true")
     ap.add_argument("--model", default="resnet50", choices=["resnet50", "resnet50-v2", "resnext50", "mobilenet-v1", "mobilenet-v2", "mobilenet-v3-large",
-                                                      "mobilenet-v3-small", "efficientnet-b0", "convnext-tiny", "vit-b16", "swin-tiny", "bert-base", "modernbert-base", "qwen3-0.6b", "gemma3-1b"])
+                                                      "mobilenet-v3-small", "efficientnet-b0", "convnext-tiny", "vit-b16", "swin-tiny", "bert-base", "modernbert-base", "t5-base-encoder", "qwen3-0.6b", "gemma3-1b"])
     ap.add_argument("--graph-tune", type=int, default=1, help="whole-graph tile re-tuning at capture (0 = off)")
     ap.add_argument("--windows", type=int, default=1,
                     help="timed windows of --iters replays each; above 1, graph_ms is their median and "
@@ -49,6 +49,14 @@ def main():
         r = s.runner("serving_default", ["input_ids", "input_mask"], ["hidden", "cls"])
         # 22 layers of GEMMs (Wqkv, Wo, Wi, MLP Wo) over S = 1024 rows + attention (8 global layers whole, 14 at 129 keys)
         flop_per_item = 2 * 22 * 768 * (4 * 768 + 3 * 1152) * 1024 + 4 * 768 * 1024 * (8 * 1024 + 14 * 129)
+    elif args.model == "t5-base-encoder":
+        from rust_tensorflow_serving2_amd.models import t5
+        if not args.model_dir:
+            t5.export(path, "t5_base_encoder", seed=0)
+        s = Servable("t5", 1, path, opts)
+        r = s.runner("serving_default", ["input_ids", "input_mask"], ["hidden", "pooled"])
+        # 12 layers of GEMMs (q, k, v, o, wi, wo) over S = 512 rows + attention over all 512 keys
+        flop_per_item = 2 * 12 * 768 * (4 * 768 + 2 * 3072) * 512 + 4 * 12 * 768 * 512 * 512
     elif args.model == "qwen3-0.6b":
         from rust_tensorflow_serving2_amd.models import qwen3
         if not args.model_dir:
@@ -124,6 +132,8 @@ def main():
                  np.zeros((b, 128), np.int32)]
         elif args.model == "modernbert-base":
             x = [rng.integers(0, 50368, (b, 1024)).astype(np.int32), np.ones((b, 1024), np.int32)]
+        elif args.model == "t5-base-encoder":
+            x = [rng.integers(0, 32128, (b, 512)).astype(np.int32), np.ones((b, 512), np.int32)]
         elif args.model in ("qwen3-0.6b", "gemma3-1b"):
             x = [rng.integers(0, 32000, (b, 1024)).astype(np.int32), np.ones((b, 1024), np.int32)]
         else:

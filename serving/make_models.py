@@ -5,7 +5,7 @@ The reference downloads ``resnet_v2_fp32_savedmodel_NHWC`` and copies version
 Offline, we write random-init SavedModels of the same architectures in the
 same ``<root>/<name>/<version>/`` layout:
 
-    python serving/make_models.py --root serving/models [--models resnet,resnet_v2,resnext50,mobilenet,mobilenet_v2,mobilenet_v3_large,mobilenet_v3_small,efficientnet_b0,convnext_tiny,vit_b16,swin_tiny,bert,gpt2,gpt2_tiny,llama,llama_tiny,llama_8b,llama_tiny_d128,qwen3,qwen3_tiny,modernbert,dlrm,half_plus_two]
+    python serving/make_models.py --root serving/models [--models resnet,resnet_v2,resnext50,mobilenet,mobilenet_v2,mobilenet_v3_large,mobilenet_v3_small,efficientnet_b0,convnext_tiny,vit_b16,swin_tiny,bert,gpt2,gpt2_tiny,llama,llama_tiny,llama_8b,llama_tiny_d128,qwen3,qwen3_tiny,modernbert,t5,dlrm,half_plus_two]
 
 * ``resnet``        ResNet-50 v1.5 (NHWC, alias "input", outputs classes/probabilities)
 * ``resnet_v2``     ResNet-50 v2 pre-activation (the fetch.sh model's architecture)
@@ -35,6 +35,10 @@ same ``<root>/<name>/<version>/`` layout:
                     S = 1024, vocabulary 50368 (pre-norm, bias-free, rotate-half RoPE in every layer, two layers in three
                     local with a +-64 band adder; input_ids / input_mask -> hidden, cls) and a 3-layer, 128-wide one at
                     S = 200 with a +-24 window
+* ``t5`` (= ``t5_base_encoder`` and ``t5_tiny``)  T5 v1.0 encoder, 768 wide, 12 layers, 12 heads of 64, ReLU FFN 3072, S = 512,
+                    vocabulary 32128 (pre-norm RMS LayerNorm, bias-free, no score scale, the relative-position bias of 32
+                    buckets up to distance 128 added with the padding adder once for all layers; input_ids / input_mask ->
+                    hidden, pooled = the masked mean) and a 3-layer, 128-wide one at S = 200
 * ``dlrm``          DLRM, Criteo layout (13 dense + 26 sparse features, D = 128, tables capped at 40000 rows: 198 MB;
                     Predict dense / sparse, Classify and Regress over tf.Examples)
 * ``half_plus_two`` TF Serving's canonical test model
@@ -58,8 +62,9 @@ def main(argv=None):
     import numpy as np
     from rust_tensorflow_serving2_amd.models import half_plus_two, resnet
     names = [m.strip() for m in args.models.split(",") if m.strip()]
-    # ``modernbert`` stands for both of its models
-    names = [n for m in names for n in (("modernbert_base", "modernbert_tiny") if m == "modernbert" else (m,))]
+    # ``modernbert`` and ``t5`` stand for both of their models
+    both = {"modernbert": ("modernbert_base", "modernbert_tiny"), "t5": ("t5_base_encoder", "t5_tiny")}
+    names = [n for m in names for n in both.get(m, (m,))]
     for m in names:
         out = os.path.join(args.root, m, str(args.version))
         if os.path.exists(os.path.join(out, "saved_model.pb")):
@@ -105,6 +110,9 @@ def main(argv=None):
         elif m in ("modernbert_base", "modernbert_tiny"):
             from rust_tensorflow_serving2_amd.models import modernbert
             modernbert.export(out, m, seed=args.seed)
+        elif m in ("t5_base_encoder", "t5_tiny"):
+            from rust_tensorflow_serving2_amd.models import t5
+            t5.export(out, m, seed=args.seed)
         elif m == "dlrm":
             from rust_tensorflow_serving2_amd.models import dlrm
             dlrm.export(out, "dlrm_criteo", seed=args.seed)
